@@ -20,7 +20,10 @@ prompt, ``--max-tokens`` (AIProvider default 500) generated tokens at
 temperature 0.3. Random-init weights (no checkpoints offline) => EOS is not
 meaningful, so generation always runs to maxTokens (``ignore_eos``).
 
-Prints ONE JSON line on rank 0.
+A plain run sets up, warms up, times ``--steps`` steps and prints ONE JSON line on
+rank 0 (``ms_per_step``: one timed step). ``--dump-outputs DIR`` also writes the last
+timed step's results as ``DIR/<name>.npy``; ``--full`` adds the checks the headline
+figure does not need (the audit of the API servers' Event records).
 """
 from __future__ import annotations
 
@@ -93,6 +96,15 @@ def parse_args():
                     help="pipelined waves: wave w+1 fails when wave w's explanations are generated (the "
                          "engine's finish hook) or once every pipeline thread has its explanation back")
     ap.add_argument("--json-out", default=None)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to its callers as "
+                         "DIR/<name>.npy (float32, one row per failure of that step in pod order, -1 = padding): "
+                         "the ranked match events (line numbers, scores, pattern ids) and the explanation "
+                         "(generated token ids; UTF-8 bytes when the engines run in other processes). "
+                         "Logs, patterns, weights and sampling seeds are the same for the same arguments")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks that the headline figure does not need: the audit of the API "
+                         "servers' Event records (detail.apiserver_audit: every failure analysed exactly once)")
     ap.add_argument("--cpu", action="store_true",
                     help="CPU rehearsal (gloo, tiny models): allows --gpus N > 1 on a host without N GPUs")
     return ap.parse_args()
@@ -163,6 +175,55 @@ def shard_read(kid, what: str) -> str:
             raise SystemExit(f"shard process {kid.pid} exited (code {kid.poll()}) before {what}")
         if line.startswith(f"{SHARD_TAG} {what}"):
             return line[len(SHARD_TAG) + len(what) + 2:].strip()
+
+
+DUMP_EVENTS = 16            # ranked match events kept per failure
+DUMP_BYTES = 60 * 2**20     # cap on everything written by --dump-outputs
+
+
+def dump_outputs(dirpath: str, suffix: str, names: list[str], captured: dict, tokens: dict, ee, max_tokens: int) -> None:
+    """``--dump-outputs``: the last timed step's results as float32 arrays, one row per
+    failure in the step's pod order (``names``). ``captured[pod] = (AnalysisResult,
+    AIProviderConfig, AIResponse)`` is what the explainer's caller held; ``tokens`` maps a
+    prompt (tuple of ids) to its generated ids when the engine runs in this process (``ee``).
+    Rows past the size cap are dropped from the end (a fixed prefix of the step's pods)."""
+    import hashlib
+
+    import numpy as np
+
+    width = max_tokens if ee is not None else 8 * max_tokens
+    per_row = 3 * DUMP_EVENTS + 3 + width
+    names = names[:max(1, DUMP_BYTES // (4 * per_row))]
+    n = len(names)
+    line = np.full((n, DUMP_EVENTS), -1, dtype=np.float32)
+    score = np.full((n, DUMP_EVENTS), -1, dtype=np.float32)
+    pat = np.full((n, DUMP_EVENTS), -1, dtype=np.float32)
+    total = np.full((n,), -1, dtype=np.float32)
+    ptoks = np.full((n,), -1, dtype=np.float32)
+    gtoks = np.full((n,), -1, dtype=np.float32)
+    expl = np.full((n, width), -1, dtype=np.float32)
+    have = [(i, captured[nm]) for i, nm in enumerate(names) if nm in captured]
+    prompts = ee.build_prompts([(res, cfg) for _, (res, cfg, _) in have]) if (ee is not None and have) else []
+    for k, (i, (res, cfg, resp)) in enumerate(have):
+        evs = res.events or []
+        total[i] = len(evs)
+        for j, e in enumerate(evs[:DUMP_EVENTS]):
+            line[i, j], score[i, j] = e.line_number, e.score
+            pid = (e.matched_pattern.id if e.matched_pattern else None) or ""
+            pat[i, j] = int(hashlib.sha1(pid.encode()).hexdigest()[:6], 16)   # 24 bits: exact in float32
+        ptoks[i] = resp.prompt_tokens if resp.prompt_tokens is not None else -1
+        gtoks[i] = resp.tokens_generated if resp.tokens_generated is not None else -1
+        if ee is not None:
+            out = tokens.get(tuple(prompts[k]), [])[:width]
+        else:
+            out = list((resp.explanation or "").encode("utf-8"))[:width]
+        expl[i, :len(out)] = out
+    os.makedirs(dirpath, exist_ok=True)
+    arrays = {"match_line_numbers": line, "match_scores": score, "match_pattern_ids": pat, "match_total_events": total,
+              "prompt_tokens": ptoks, "tokens_generated": gtoks,
+              ("explanation_tokens" if ee is not None else "explanation_utf8"): expl}
+    for name, arr in arrays.items():
+        np.save(os.path.join(dirpath, f"{name}{suffix}.npy"), arr)
 
 
 def main() -> int:
@@ -329,6 +390,21 @@ def main() -> int:
     init_s = time.perf_counter() - t_init
     note(f"init done in {init_s:.1f} s")
 
+    # --dump-outputs: what the callers of the last timed wave receive, kept from the moment
+    # that wave starts (pod name -> result / provider config / response; prompt -> generated ids)
+    dump = {"on": False, "captured": {}, "tokens": {}}
+    if a.dump_outputs and llm is not None:
+        dump_inner = llm.finish_hook
+
+        def dump_hook(reqs) -> None:
+            if dump_inner is not None:
+                dump_inner(reqs)
+            if dump["on"]:
+                for r in reqs:
+                    dump["tokens"][tuple(r.prompt)] = list(r.output)
+
+        llm.finish_hook = dump_hook
+
     def engine_stats() -> dict:
         """Prefill / decode token counters, prefill graph buckets and DFA size, summed
         over the engine processes (or read from the in-process engines)."""
@@ -421,7 +497,10 @@ def main() -> int:
 
             def explain(self, result, cfg):
                 try:
-                    return self.inner.explain(result, cfg)
+                    resp = self.inner.explain(result, cfg)
+                    if dump["on"]:
+                        dump["captured"][result.pod_name] = (result, cfg, resp)
+                    return resp
                 finally:
                     count_explained()
 
@@ -509,6 +588,7 @@ def main() -> int:
             (all analyses stored, kube writes drained) inside the timed region."""
             if a.serial_waves:
                 for w in ws:
+                    dump["on"] = bool(a.dump_outputs) and w == ws[-1]
                     run_wave(w)
                 return
             with lock:
@@ -516,6 +596,7 @@ def main() -> int:
                 done_ev.clear()
             base = handed()
             for j, w in enumerate(ws):
+                dump["on"] = bool(a.dump_outputs) and w == ws[-1]
                 inject(w)
                 if j + 1 < len(ws):
                     with exp_cv:
@@ -534,15 +615,26 @@ def main() -> int:
         def run_wave(w: int) -> None:
             t0 = time.perf_counter()
             res = meng.analyze(logs[w], [(f"app-{w}-{i}", "default") for i in range(a.batch)])
+            dump["on"] = bool(a.dump_outputs) and w == waves - 1
             outs = ee.explain_many([(r, cfg) for r in res])
             for r, o in zip(res, outs):
                 _ = pattern_annotation(r) if isinstance(o, Exception) else o.explanation
                 lat.append(time.perf_counter() - t0)
+                if dump["on"] and not isinstance(o, Exception):
+                    dump["captured"][r.pod_name] = (r, cfg, o)
             counter["outcomes"]["ai-complete"] = counter["outcomes"].get("ai-complete", 0) + len(outs)
 
         def run_timed(ws: list[int]) -> None:
             for w in ws:
                 run_wave(w)
+
+    def write_dump() -> None:
+        if not a.dump_outputs or not waves:
+            return
+        last = names_by_wave[-1] if a.mode == "pipeline" else [f"app-{waves - 1}-{i}" for i in range(a.batch)]
+        suffix = "" if (rank == 0 and shard == 0) else f".rank{rank}.shard{shard}"
+        dump_outputs(a.dump_outputs, suffix, last, dump["captured"], dump["tokens"], ee, a.max_tokens)
+        note(f"outputs of the last timed wave written to {a.dump_outputs}")
 
     # a progress line on stderr every 30 s (stdout stays the ONE JSON line)
     prog_stop = threading.Event()
@@ -576,6 +668,7 @@ def main() -> int:
         mono1 = time.monotonic_ns()
         prog_stop.set()
         st1 = engine_stats()
+        write_dump()
         print(f"{SHARD_TAG} RESULT " + json.dumps({
             "t0": mono0, "t1": mono1, "lat": lat, "outcomes": counter["outcomes"],
             "ptoks": st1["prefill_tokens"] - stats0["prefill_tokens"],
@@ -628,8 +721,8 @@ def main() -> int:
         for d in allo:
             for o, n in d.items():
                 job_outcomes[o] = job_outcomes.get(o, 0) + n
-    audit = None
-    if a.mode == "pipeline" and (rank == grp0 or not rest):
+    audit = None   # --full only: a plain run does not read the servers' Events back
+    if a.full and a.mode == "pipeline" and (rank == grp0 or not rest):
         per_pod: dict[str, int] = {}
         for ev in fk.list(EVENTS, "default"):
             reg = ev.get("regarding") or {}
@@ -639,7 +732,7 @@ def main() -> int:
         counts = list(per_pod.values())
         audit = {"pods_with_complete_event": len(per_pod), "max_complete_events_per_pod": max(counts, default=0),
                  "expected_pods": a.batch * waves * (grp_n if rest else 1)}   # inproc: this process's shard
-    if rest and world > 1:   # every API server's own record, merged (group leaders audited theirs)
+    if a.full and rest and world > 1:   # every API server's own record, merged (group leaders audited theirs)
         alla: list = [None] * world
         dist.all_gather_object(alla, audit)
         parts = [x for x in alla if x is not None]
@@ -723,6 +816,7 @@ def main() -> int:
     }
     if share:
         out["detail"]["shared_gpu_rehearsal"] = True
+    write_dump()
     if rank == 0:
         print(json.dumps(out), flush=True)
         if a.json_out:

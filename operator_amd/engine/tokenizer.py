@@ -134,10 +134,13 @@ class Tokenizer:
             tr = trainers.BpeTrainer(vocab_size=vocab, show_progress=False,
                                      initial_alphabet=pre_tokenizers.ByteLevel.alphabet())
             tk.train_from_iterator(_corpus(), trainer=tr)
-            _CACHE.mkdir(parents=True, exist_ok=True)
-            tmp = f.with_suffix(f".{os.getpid()}.tmp")
-            tk.save(str(tmp))
-            os.replace(tmp, f)
+            try:   # the cache is an optimisation: a read-only tree trains again next start
+                _CACHE.mkdir(parents=True, exist_ok=True)
+                tmp = f.with_suffix(f".{os.getpid()}.tmp")
+                tmp.write_text(tk.to_str(), encoding="utf-8")
+                os.replace(tmp, f)
+            except OSError:
+                pass
             return tk
 
     def encode_chat(self, messages: list[dict]) -> list[int]:

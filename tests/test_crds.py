@@ -1,5 +1,6 @@
 """CRD schema parity with the reference manifests (structure, types, enums,
 defaults, required, names), ignoring description text."""
+import json
 import os
 
 import pytest
@@ -8,7 +9,9 @@ import yaml
 from operator_amd.api import crds
 from operator_amd.api.models import AIProvider, PatternLibrary, Podmortem
 
-REF = "/root/reference/src/main/kubernetes"
+# the reference manifests' metadata and spec with the description text stripped, one
+# snapshot per CRD (tests/golden/crds/<name>.json)
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "crds")
 
 
 def _strip(o):
@@ -23,11 +26,8 @@ def _strip(o):
                                       ("patternlibrary-crd.yaml", crds.patternlibrary_crd),
                                       ("aiprovider-crd.yaml", crds.aiprovider_crd)])
 def test_crd_matches_reference(fname, fn):
-    path = os.path.join(REF, fname)
-    if not os.path.exists(path):
-        pytest.skip("reference manifests not mounted")
-    with open(path) as f:
-        ref = yaml.safe_load(f)
+    with open(os.path.join(GOLDEN, fname.replace(".yaml", ".json"))) as f:
+        ref = json.load(f)
     ours = fn()
     assert ours["metadata"] == ref["metadata"]
     assert _strip(ours["spec"]) == _strip(ref["spec"])

@@ -293,3 +293,22 @@ def test_streaming_detokenization_is_exact_or_off(tmp_path):
     for r in reqs:
         hook([r])
         assert tok.text_of(r.detok) == tok.decode(r.output)
+
+
+def test_trained_tokenizer_without_a_writable_cache(tmp_path, monkeypatch):
+    """The tokenizer cache is an optimisation: where it cannot be written (an installed,
+    read-only tree) the tokenizer is trained in memory and encodes as the cached one does."""
+    from operator_amd.engine import tokenizer as tkmod
+
+    cfg = get_config("tiny")
+    blocker = tmp_path / "not-a-directory"
+    blocker.write_text("x")
+    monkeypatch.setattr(tkmod, "_CACHE", blocker / "cache")   # mkdir under a file: OSError for any user
+    t = tkmod.Tokenizer(cfg.vocab_size, cfg.bos_id, cfg.eos_ids[0])
+    assert not (blocker / "cache").exists()
+    monkeypatch.setattr(tkmod, "_CACHE", tmp_path / "cache")
+    cached = tkmod.Tokenizer(cfg.vocab_size, cfg.bos_id, cfg.eos_ids[0])    # trains and writes
+    reloaded = tkmod.Tokenizer(cfg.vocab_size, cfg.bos_id, cfg.eos_ids[0])  # reads the file back
+    assert list((tmp_path / "cache").glob("tokenizer-*.json"))
+    text = "java.lang.OutOfMemoryError: Java heap space; pod restarted 3 times"
+    assert t.encode(text) == cached.encode(text) == reloaded.encode(text)

@@ -109,18 +109,21 @@ def test_oneshot_disabled_without_gpu():
     assert g.all_reduce_(t) is t
 
 
-def test_bench_self_launches_ranks():
+def test_bench_self_launches_ranks(tmp_path):
     """`python bench.py --gpus 2` with no outer torchrun starts its two rank processes
-    itself (127.0.0.1 rendezvous); the JSON line reports the 2-rank job, not one rank."""
+    itself (127.0.0.1 rendezvous); the JSON line reports the 2-rank job, not one rank.
+    --dump-outputs: each rank writes its last timed wave's results (float32 rows per failure)."""
     import json
     import subprocess
     import sys
+
+    import numpy as np
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--cpu", "--steps", "1", "--warmup", "1",
            "--model", "tiny", "--batch", "3", "--max-tokens", "4", "--prompt-tokens", "128", "--log-kb", "4",
-           "--patterns", "40"]
+           "--patterns", "40", "--dump-outputs", str(tmp_path)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
@@ -130,6 +133,12 @@ def test_bench_self_launches_ranks():
     assert out["detail"]["rccl_world"] == 2 and out["detail"]["launcher"] == "bench.py"
     assert len(out["detail"]["per_rank_elapsed_s"]) == 2
     assert out["detail"]["outcomes"] == {"ai-complete": 3}   # rank 0's own wave
+    assert out["ms_per_step"] > 0 and out["detail"]["apiserver_audit"] is None   # the audit is --full's
+    for sfx in ("", ".rank1.shard0"):
+        toks = np.load(tmp_path / f"explanation_tokens{sfx}.npy")
+        assert toks.dtype == np.float32 and toks.shape == (3, 4) and (toks >= 0).all()
+        assert (np.load(tmp_path / f"tokens_generated{sfx}.npy") == 4).all()
+        assert np.load(tmp_path / f"match_scores{sfx}.npy").shape == (3, 16)
 
 
 def test_bench_refuses_missing_gpus():
@@ -193,7 +202,7 @@ def test_bench_eight_ranks_gloo_one_apiserver():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"),
            "--gpus", "8", "--steps", "1", "--warmup", "1", "--model", "tiny", "--batch", "3",
-           "--max-tokens", "4", "--prompt-tokens", "128", "--log-kb", "4", "--patterns", "40"]
+           "--max-tokens", "4", "--prompt-tokens", "128", "--log-kb", "4", "--patterns", "40", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
