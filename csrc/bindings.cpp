@@ -331,6 +331,36 @@ void gemm_pp(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::T
                    cur_stream(), one_seg, wsp, flp));
 }
 
+void gemm_w4(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& y_opt,
+             const c10::optional<at::Tensor>& p, int64_t splits, bool silu_gu) {
+  CHECK_DEV(x); CHECK_BF16(x); CHECK_BF16(w); CHECK_CONTIG(x); CHECK_CONTIG(w);
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && w.size(1) == x.size(1), "x [M,K], w [N,K]");
+  const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
+  TORCH_CHECK(M == 256, "gemm_w4: M == 256");
+  TORCH_CHECK(N >= 128 && N % 128 == 0, "gemm_w4: N % 128 == 0");
+  TORCH_CHECK(K >= 64 && K % 64 == 0 && K < (1LL << 22), "gemm_w4: K % 64 == 0, K < 2^22");
+  TORCH_CHECK(splits >= 1 && splits <= 16 && splits <= K / 64, "gemm_w4: 1 <= splits <= min(16, K / 64)");
+  TORCH_CHECK(!silu_gu || splits == 1, "gemm_w4: fused SwiGLU needs splits == 1");
+  bf16_t* yp = nullptr;
+  if (y_opt.has_value()) {
+    CHECK_DEV(*y_opt); CHECK_BF16(*y_opt); CHECK_CONTIG(*y_opt);
+    TORCH_CHECK(y_opt->dim() == 2 && y_opt->size(0) == M && y_opt->size(1) == (silu_gu ? N / 2 : N), "gemm_w4: y");
+    yp = ptr<bf16_t>(*y_opt);
+  } else {
+    TORCH_CHECK(splits > 1 && !silu_gu, "y may be omitted only for split-K slabs summed by the consumer");
+  }
+  float* pp = nullptr;
+  if (splits > 1) {
+    TORCH_CHECK(p.has_value(), "split-K needs a partial buffer");
+    CHECK_DEV(*p); CHECK_DT(*p, at::kFloat); CHECK_CONTIG(*p);
+    TORCH_CHECK(p->numel() >= splits * M * N, "partial buffer too small");
+    pp = p->data_ptr<float>();
+  }
+  TORCH_CHECK(N * K < (1LL << 40), "gemm too large");
+  const c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
+  RC(oamd::gemm_w4(ptr<bf16_t>(x), ptr<bf16_t>(w), yp, pp, (int)M, (int)N, (int)K, (int)splits, silu_gu, cur_stream()));
+}
+
 void gemm_skinny(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& y_opt,
                  const c10::optional<at::Tensor>& p, int64_t splits, bool silu_gu) {
   CHECK_DEV(x); CHECK_BF16(x); CHECK_BF16(w); CHECK_CONTIG(x); CHECK_CONTIG(w);
@@ -654,6 +684,8 @@ PYBIND11_MODULE(_C, m) {
         pybind11::arg("p") = pybind11::none(), pybind11::arg("splits") = 1, pybind11::arg("bm") = 256,
         pybind11::arg("silu_gu") = false, pybind11::arg("nt") = true, pybind11::arg("one_seg") = false,
         pybind11::arg("sk_ws") = pybind11::none(), pybind11::arg("sk_flags") = pybind11::none());
+  m.def("gemm_w4", &gemm_w4, pybind11::arg("x"), pybind11::arg("w"), pybind11::arg("y"),
+        pybind11::arg("p") = pybind11::none(), pybind11::arg("splits") = 1, pybind11::arg("silu_gu") = false);
   m.def("gemm_pp_sk_grid", &oamd::gemm_pp_sk_grid, pybind11::arg("tiles"), pybind11::arg("steps"));
   m.def("gemm_skinny", &gemm_skinny, pybind11::arg("x"), pybind11::arg("w"), pybind11::arg("y"),
         pybind11::arg("p") = pybind11::none(), pybind11::arg("splits") = 1, pybind11::arg("silu_gu") = false);

@@ -48,6 +48,11 @@ int gemm_tile(const bf16_t* X, const bf16_t* W, bf16_t* Y, const bf16_t* bias, i
 int gemm_pp(const bf16_t* X, const bf16_t* W, bf16_t* Y, float* P, int M, int N, int K, int S, int bm, bool silu_gu,
             bool nt, hipStream_t stream, bool one_seg = false, float* ws = nullptr, int* flags = nullptr);
 int gemm_pp_sk_grid(int tiles, int steps);
+// Four-wave 256-row decode GEMM (gemm_w4.hip): M == 256, N % 128 == 0, K % 64 == 0, S <= min(16, K / 64)
+// K slices by gemm_decode's rule (fp32 slabs P[S][256][N]; reduced into Y unless Y is nullptr); silu_gu: fused
+// SwiGLU (S == 1), Y [256, N/2]. Bitwise equal to gemm_decode (bm 256, bn 128) / gemm_pp (bm 256).
+int gemm_w4(const bf16_t* X, const bf16_t* W, bf16_t* Y, float* P, int M, int N, int K, int S, bool silu_gu,
+            hipStream_t stream);
 // 256-row decode GEMM with register-streamed activations (gemm_xr.hip): Xt = X [256, K] in the tiled
 // layout [16][K/32][64][8]; N % 128 == 0, K % (64 S) == 0; epi 0 = fp32 slabs P[S][256][N], 1 = bf16 Y,
 // 2 = SwiGLU (interleaved gate|up, S == 1) Y [256, N/2], 3 = the same written tiled.

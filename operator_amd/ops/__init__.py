@@ -109,6 +109,14 @@ def gate_up_silu(x: torch.Tensor, wgu: torch.Tensor, block: int | None) -> torch
     if (x.is_cuda and block == 64 and x.dtype == torch.bfloat16 and M % 64 == 0 and M <= 256 and N % 128 == 0
             and K % 64 == 0 and x.is_contiguous() and wgu.is_contiguous()):
         t = _gemm_table_get().get(("silu", M, N, K))
+        if t == "w4":   # four-wave 256-row kernel (gemm_w4.hip); the parent plan of the 256-row bucket is pp256
+            if M != 256:
+                raise ValueError(f"gemm table: plan 'w4' on silu,{M},{N},{K}: gemm_w4 takes the 256-row bucket only")
+            if DEC_GEMM_W4:
+                y = torch.empty(M, N // 2, dtype=x.dtype, device=x.device)
+                kernels().gemm_w4(x, wgu, y, None, 1, True)
+                return y
+            t = "pp256"
         if isinstance(t, str) and t.startswith("pp"):   # ping-pong kernel, nt weight loads (bm 128 / 256)
             y = torch.empty(M, N // 2, dtype=x.dtype, device=x.device)
             bm = int(t[2:])
@@ -130,6 +138,9 @@ def gate_up_silu(x: torch.Tensor, wgu: torch.Tensor, block: int | None) -> torch
 # CU over the flattened (tile, K-step) stream instead of one block per 128-feature tile (224 of 256 CUs
 # busy at the 8B shape). OAMD_PP_STREAM_K=1 turns it on (A/B runs).
 PP_STREAM_K = os.environ.get("OAMD_PP_STREAM_K", "0") == "1"
+# Table plans tagged "w4" run the four-wave 256-row decode GEMM (csrc/kernels/gemm_w4.hip, bitwise equal to
+# the parent plan's kernel); OAMD_DEC_GEMM_W4=0 runs the parent plan instead (A/B runs).
+DEC_GEMM_W4 = os.environ.get("OAMD_DEC_GEMM_W4", "1") != "0"
 _PP_SK_WS: dict = {}
 
 
@@ -363,7 +374,7 @@ def skinny_plan(M: int, N: int, K: int) -> int | None:
 
 # Every GPU GEMM of the model runs on the hand-written gfx950 kernels: prefill projections (M > 256
 # rows) on gemm_tile's persistent p5 schedule (csrc/kernels/gemm_tile.hip), decode buckets on
-# gemm_pp / gemm_tn / gemm_skinny, the lm_head on gemm_tile, fp8 on gemm_fp8. hipBLASLt is reached
+# gemm_pp / gemm_tn / gemm_w4 / gemm_skinny, the lm_head on gemm_tile, fp8 on gemm_fp8. hipBLASLt is reached
 # only by shapes none of them takes (K % 64 != 0, N % 16 != 0, non-bf16), counted in BLAS_CALLS.
 # OAMD_PREFILL_BLAS=1 routes the plain prefill projections (QKV, O, down) to hipBLASLt instead, for
 # A/B runs against the vendor library (profiles/gemm_tile_p5_vs_hipblaslt_r6.jsonl).
@@ -452,10 +463,22 @@ def linear(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor | None = None, sp
         if tile_ok(x, w) and tile_out_ok(out):
             return linear_tile(x, w, out)
         return _blas(x, w, out, None)
+    # a fifth element "w4": the table plan runs on gemm_w4 (the first four stay its parent gemm_decode plan)
+    if len(plan) > 4 and plan[4] == "w4" and (M != 256 or tuple(plan[:2]) != (256, 128)):
+        raise ValueError(f"gemm table: plan {plan} on {M},{N},{K}: gemm_w4 runs M = 256 as 256 x 128 tiles only")
+    w4 = (DEC_GEMM_W4 and len(plan) > 4 and plan[4] == "w4" and bm is None and bn is None
+          and splits is None and stages is None)
     bm, bn, S = bm or plan[0], bn or plan[1], splits or plan[2]
     ns = stages or (plan[3] if len(plan) > 3 else 3)
     if S > 1 and (partial is None or partial.numel() < S * M * N):
         partial = torch.empty(S * M * N, dtype=torch.float32, device=x.device)
+    if w4:
+        if defer_reduce and S > 1 and out is None:
+            kernels().gemm_w4(x, w, None, partial, S, False)
+            return SplitK(partial, S, M, N)
+        y = out if out is not None else torch.empty(M, N, dtype=x.dtype, device=x.device)
+        kernels().gemm_w4(x, w, y, partial if S > 1 else None, S, False)
+        return y
     if defer_reduce and S > 1 and out is None:
         kernels().gemm_decode(x, w, None, partial, S, bn, bm, False, False, ns)
         return SplitK(partial, S, M, N)

@@ -9,6 +9,7 @@ profiles/decode_gemm_dw_vs_table_m256_cold.jsonl, and deleted.)
 One JSON line per shape.
 
     python tools/bench_decode_gemm.py [--m 256] [--rounds 5]
+    python tools/bench_decode_gemm.py --w4      # parent plan against the four-wave gemm_w4, [min, max] per arm
 """
 from __future__ import annotations
 
@@ -49,6 +50,9 @@ def main() -> int:
     ap.add_argument("--out", default=None)
     ap.add_argument("--tile", action="store_true",
                     help="also time the 256x256-tile kernel (gemm_tile) with split-K S = 1, 2, 4, 8, 16")
+    ap.add_argument("--w4", action="store_true",
+                    help="M = 256: time the parent plan against the four-wave kernel (gemm_w4) instead of the table")
+    ap.add_argument("--w4-splits", default="qkv=5,o=8,down=8", help="K slices of the w4 arm per shape")
     a = ap.parse_args()
     M = a.m
     rows = []
@@ -77,6 +81,31 @@ def main() -> int:
             norm = lambda r: ops.rmsnorm(r, nw, 1e-5, residual=res, out=yn)  # noqa: E731
             cands["table"] = lambda: ops.linear(x, nxt(), defer_reduce=True)
             cands["table+norm"] = lambda: norm(ops.linear(x, nxt(), defer_reduce=True))
+        if a.w4 and M == 256:
+            # parent plan against the four-wave kernel (gemm_w4.hip), both through ops.linear /
+            # ops.gate_up_silu: "parent" = the table plan with OAMD_DEC_GEMM_W4=0, "w4" = the plan
+            # tagged w4 with the slice count of --w4-splits
+            tab = ops._gemm_table_get()
+            key = ("silu", M, N, K) if silu else (M, N, K)
+            base = tab.get(key)
+            S4 = {k: int(v) for k, v in (kv.split("=") for kv in a.w4_splits.split(","))}.get(name, 1)
+            if silu:
+                w4_plan = "w4"
+            else:
+                b = list(base[:4]) if isinstance(base, (list, tuple)) else [256, 128, S4, 3]
+                w4_plan = [256, 128, S4, b[3] if len(b) > 3 else 3, "w4"]
+
+            def arm(plan, flag, fn):
+                def run():
+                    tab[key], ops.DEC_GEMM_W4 = plan, flag
+                    return fn()
+                return run
+
+            table_arms = dict(cands)
+            cands = {}
+            for k, fn in table_arms.items():
+                cands[k.replace("table", "parent")] = arm(base, False, fn)
+                cands[k.replace("table", "w4")] = arm(w4_plan, True, fn)
         if a.tile:
             C = ops.kernels()
             P = torch.empty(16 * M * N, dtype=torch.float32, device="cuda")
@@ -99,8 +128,12 @@ def main() -> int:
             for k, fn in cands.items():
                 times[k].append(timeit(fn, a.iters))
         us = {k: round(statistics.median(v), 2) for k, v in times.items()}
+        first = next(iter(us))
         r = {"M": M, "shape": name, "N": N, "K": K, "weight_copies": ncopy, "us": us,
-             "weight_tb_s": round(N * K * 2 / us["table"] / 1e6, 2)}
+             "us_range": {k: [round(min(v), 2), round(max(v), 2)] for k, v in times.items()},
+             "weight_tb_s": round(N * K * 2 / us[first] / 1e6, 2)}
+        if a.w4 and M == 256:
+            r["w4_splits"] = S4
         print(json.dumps(r), flush=True)
         rows.append(r)
         del ws
