@@ -395,6 +395,9 @@ void gemm_skinny(const at::Tensor& x, const at::Tensor& w, const c10::optional<a
 void quantize_fp8(const at::Tensor& x, at::Tensor& q, at::Tensor& sx) {
   CHECK_DEV(x); CHECK_BF16(x); CHECK_CONTIG(q); CHECK_CONTIG(sx); CHECK_DT(sx, at::kFloat);
   TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1, "x must be [M, K] row-major");
+  // the kernels read 16 B per lane: every row must start on a 16-B boundary
+  TORCH_CHECK(x.stride(0) % 8 == 0 && reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "quantize_fp8: x needs a 16-B aligned base and a row stride that is a multiple of 8 elements");
   TORCH_CHECK(q.scalar_type() == at::kByte || q.scalar_type() == at::kFloat8_e4m3fn, "q must be uint8 / e4m3fn");
   const int64_t M = x.size(0), K = x.size(1);
   TORCH_CHECK(q.numel() == M * K && sx.numel() == M && K % 8 == 0, "quantize_fp8 shapes");
@@ -420,6 +423,8 @@ void silu_quantize_fp8(const at::Tensor& gu, at::Tensor& q, at::Tensor& sx, cons
     pp = slabs->data_ptr<float>();
   } else {
     CHECK_BF16(gu);
+    TORCH_CHECK(gu.stride(0) % 8 == 0 && reinterpret_cast<uintptr_t>(gu.data_ptr()) % 16 == 0,
+                "silu_quantize_fp8: gu needs a 16-B aligned base and a row stride that is a multiple of 8 elements");
   }
   const c10::hip::HIPGuardMasqueradingAsCUDA g(gu.device());
   RC(oamd::silu_quantize_fp8(pp != nullptr ? nullptr : ptr<bf16_t>(gu), pp, (int)splits,

@@ -652,7 +652,8 @@ __global__ void __launch_bounds__(1024) attn_decode_combine_q8_kernel(
   for (int i = 0; i < MAXV; ++i) {
     const int e = tid + i * NT;
     if (e < n) {
-      const int pk = __builtin_amdgcn_cvt_pk_fp8_f32(v[i] * inv, 0.f, 0, false);
+      // a tiny row (1 / sc overflows) is divided exactly, as quantize_fp8_rows does (gemm_fp8.hip)
+      const int pk = __builtin_amdgcn_cvt_pk_fp8_f32(inv < INFINITY ? v[i] * inv : v[i] / sc, 0.f, 0, false);
       qr[e] = static_cast<uint8_t>(pk & 0xff);
     }
   }

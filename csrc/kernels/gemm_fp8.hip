@@ -142,6 +142,11 @@ __global__ void __launch_bounds__(f8::kWaves * 64, 1)
 }
 
 // Per-row dynamic quantization: sx[m] = max|x[m, :]| / 448, q = e4m3fn(x / sx).
+// The quotient is taken as x * (1 / sx), one multiply per element. Tiny rows: a non-zero row
+// whose amax is below ~1.3e-36 has a subnormal sx under 2^-128, so 1 / sx overflows to inf
+// (every element would encode inf or 0 * inf = NaN). Such a row is divided exactly, x / sx,
+// in a block-uniform branch of its own: sx stays amax / 448 (no floor), its largest element
+// still encodes +-448, and the bytes and scales of every other row are unchanged.
 // One 256-thread block per row. Rows of up to 256 x 8 x MAXV elements are loaded ONCE
 // into registers (all loads in flight together), reduced, then quantized from the
 // registers: a decode row is latency-bound, and the former two streaming passes with
@@ -234,18 +239,23 @@ __global__ void __launch_bounds__(256) quantize_rows_reg_kernel(const bf16_t* __
   const float inv = 1.f / s;
   if (threadIdx.x == 0) sx[m] = s;
   uint8_t* qr = q + m * (int64_t)K;
+  auto store = [&](auto scaled) {
 #pragma unroll
-  for (int i = 0; i < MAXV; ++i) {
-    const int vi = threadIdx.x + i * 256;
-    if (vi < nv) {
-      int lo = 0, hi = 0;
-      lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[i][0] * inv, v[i][1] * inv, lo, false);
-      lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[i][2] * inv, v[i][3] * inv, lo, true);
-      hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[i][4] * inv, v[i][5] * inv, hi, false);
-      hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[i][6] * inv, v[i][7] * inv, hi, true);
-      *reinterpret_cast<uint2*>(qr + vi * 8) = make_uint2(static_cast<uint32_t>(lo), static_cast<uint32_t>(hi));
+    for (int i = 0; i < MAXV; ++i) {
+      const int vi = threadIdx.x + i * 256;
+      if (vi < nv) {
+        int lo = 0, hi = 0;
+        lo = __builtin_amdgcn_cvt_pk_fp8_f32(scaled(v[i][0]), scaled(v[i][1]), lo, false);
+        lo = __builtin_amdgcn_cvt_pk_fp8_f32(scaled(v[i][2]), scaled(v[i][3]), lo, true);
+        hi = __builtin_amdgcn_cvt_pk_fp8_f32(scaled(v[i][4]), scaled(v[i][5]), hi, false);
+        hi = __builtin_amdgcn_cvt_pk_fp8_f32(scaled(v[i][6]), scaled(v[i][7]), hi, true);
+        *reinterpret_cast<uint2*>(qr + vi * 8) = make_uint2(static_cast<uint32_t>(lo), static_cast<uint32_t>(hi));
+      }
     }
-  }
+  };
+  // block-uniform: every row but a tiny one (header comment) takes the multiply
+  if (inv < INFINITY) store([&](float e) { return e * inv; });
+  else store([&](float e) { return e / s; });
 }
 
 // Rows longer than the register path: two streaming passes.
@@ -268,18 +278,22 @@ __global__ void quantize_fp8_rows_kernel(const bf16_t* __restrict__ x, uint8_t* 
   const float inv = 1.f / s;
   if (threadIdx.x == 0) sx[m] = s;
   uint8_t* qr = q + m * (int64_t)K;
-  for (int c = threadIdx.x * 8; c < K; c += 256 * 8) {
-    const u16x8 v = *reinterpret_cast<const u16x8*>(xr + c);
-    uint2 o;
-    int lo = 0, hi = 0;
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[0]) * inv, bf2f(v[1]) * inv, lo, false);
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[2]) * inv, bf2f(v[3]) * inv, lo, true);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[4]) * inv, bf2f(v[5]) * inv, hi, false);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[6]) * inv, bf2f(v[7]) * inv, hi, true);
-    o.x = static_cast<uint32_t>(lo);
-    o.y = static_cast<uint32_t>(hi);
-    *reinterpret_cast<uint2*>(qr + c) = o;
-  }
+  auto store = [&](auto scaled) {
+    for (int c = threadIdx.x * 8; c < K; c += 256 * 8) {
+      const u16x8 v = *reinterpret_cast<const u16x8*>(xr + c);
+      uint2 o;
+      int lo = 0, hi = 0;
+      lo = __builtin_amdgcn_cvt_pk_fp8_f32(scaled(bf2f(v[0])), scaled(bf2f(v[1])), lo, false);
+      lo = __builtin_amdgcn_cvt_pk_fp8_f32(scaled(bf2f(v[2])), scaled(bf2f(v[3])), lo, true);
+      hi = __builtin_amdgcn_cvt_pk_fp8_f32(scaled(bf2f(v[4])), scaled(bf2f(v[5])), hi, false);
+      hi = __builtin_amdgcn_cvt_pk_fp8_f32(scaled(bf2f(v[6])), scaled(bf2f(v[7])), hi, true);
+      o.x = static_cast<uint32_t>(lo);
+      o.y = static_cast<uint32_t>(hi);
+      *reinterpret_cast<uint2*>(qr + c) = o;
+    }
+  };
+  if (inv < INFINITY) store([&](float e) { return e * inv; });   // tiny rows divide: see quantize_rows_reg_kernel
+  else store([&](float e) { return e / s; });
 }
 
 int quantize_fp8_rows(const bf16_t* x, uint8_t* q, float* sx, int M, int K, int64_t ld, hipStream_t stream) {

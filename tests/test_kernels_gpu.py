@@ -373,10 +373,22 @@ def test_rmsnorm_sums_splitk_slabs(S, N):
     w = _rand(N)
     r1 = _rand(M, N)
     r2 = r1.clone()
+    r0 = r1.clone()
     y1 = ops.rmsnorm(ops.SplitK(P, S, M, N), w, 1e-5, residual=r1)
     y2 = ops.rmsnorm(ops.SplitK(P, S, M, N).materialize(), w, 1e-5, residual=r2)
     torch.testing.assert_close(r1.float(), r2.float(), atol=2e-2, rtol=1e-2)
     torch.testing.assert_close(y1.float(), y2.float(), atol=2e-2, rtol=2e-2)
+    # against the slabs added in slab order in fp32 and rounded once (what the kernel sums; torch's
+    # .sum(0) in materialize() is free to associate differently) the updated residual is the same
+    # bf16 add on every path: bit-equal. y is not promised bitwise (the 512-thread path reduces the
+    # sum of squares in another order)
+    a = P.view(S, M, N)[0].clone()
+    for k in range(1, S):
+        a += P.view(S, M, N)[k]
+    r3 = r0.clone()
+    y3 = ops.rmsnorm(a.to(torch.bfloat16), w, 1e-5, residual=r3)
+    assert torch.equal(r1.view(torch.int16), r3.view(torch.int16))
+    torch.testing.assert_close(y1.float(), y3.float(), atol=2e-2, rtol=2e-2)
 
 
 def test_deferred_splitk_decode_matches_plain():
@@ -494,6 +506,9 @@ def test_rope_kv_writes_fp8_cache():
     torch.testing.assert_close(vd, vb.cpu().float(), atol=0.07 * v_scale, rtol=0.07)
     exact = ref.kv_store(vb.cpu().float(), torch.float8_e4m3fn, v_scale)
     assert torch.equal(vc.cpu().view(torch.uint8), exact.view(torch.uint8))
+    # K too: with a power-of-two scale the stored byte is exactly e4m3(bf16 rotated k / k_scale)
+    exact_k = ref.kv_store(kb.cpu().float(), torch.float8_e4m3fn, k_scale)
+    assert torch.equal(kc.cpu().view(torch.uint8), exact_k.view(torch.uint8))
 
 
 @pytest.mark.parametrize("Hq,Hkv,splits,variant", [(8, 1, 8, 0), (8, 1, 1, 0), (32, 8, 4, 0), (64, 8, 2, 2),
