@@ -609,7 +609,7 @@ void attn_prefill(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
 
 void sample(const at::Tensor& logits, const at::Tensor& temperature, const at::Tensor& seeds,
             const at::Tensor& positions, at::Tensor& out, int64_t col_offset,
-            const c10::optional<at::Tensor>& out_val) {
+            const c10::optional<at::Tensor>& out_val, const c10::optional<at::Tensor>& thr) {
   CHECK_DEV(logits);
   TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "logits must be [rows, vocab] row-major");
   TORCH_CHECK(logits.scalar_type() == at::kFloat || logits.scalar_type() == at::kBFloat16, "logits dtype");
@@ -621,10 +621,35 @@ void sample(const at::Tensor& logits, const at::Tensor& temperature, const at::T
     CHECK_DT(*out_val, at::kFloat);
     TORCH_CHECK(out_val->numel() == rows, "out_val shape");
   }
+  if (thr.has_value()) {   // the filtered sampler: columns with logit >= thr[row]
+    CHECK_DEV(*thr); CHECK_DT(*thr, at::kFloat); CHECK_CONTIG(*thr);
+    TORCH_CHECK(thr->numel() == rows, "thr shape");
+  }
   const c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
   RC(oamd::sample_tokens(logits.data_ptr(), logits.scalar_type() == at::kBFloat16, logits.stride(0), (int)rows,
                          (int)logits.size(1), ptr<float>(temperature), ptr<int64_t>(seeds), ptr<int64_t>(positions),
-                         ptr<int64_t>(out), col_offset, optr<float>(out_val), cur_stream()));
+                         ptr<int64_t>(out), col_offset, optr<float>(out_val), cur_stream(), optr<float>(thr)));
+}
+
+// thr[row] = the top-k / top-p threshold of each row (kernels.h sample_threshold); kept: optional counts.
+void sample_threshold(const at::Tensor& logits, const at::Tensor& temperature, const at::Tensor& top_k,
+                      const at::Tensor& top_p, at::Tensor& thr, const c10::optional<at::Tensor>& kept) {
+  CHECK_DEV(logits);
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "logits must be [rows, vocab] row-major");
+  TORCH_CHECK(logits.scalar_type() == at::kFloat || logits.scalar_type() == at::kBFloat16, "logits dtype");
+  const int64_t rows = logits.size(0);
+  for (const at::Tensor* t : {&temperature, &top_k, &top_p, (const at::Tensor*)&thr}) { CHECK_DEV(*t); CHECK_CONTIG(*t); }
+  CHECK_DT(temperature, at::kFloat); CHECK_DT(top_k, at::kInt); CHECK_DT(top_p, at::kFloat); CHECK_DT(thr, at::kFloat);
+  TORCH_CHECK(temperature.numel() == rows && top_k.numel() == rows && top_p.numel() == rows && thr.numel() == rows,
+              "sampler per-row tensor shape");
+  if (kept.has_value()) {
+    CHECK_DEV(*kept); CHECK_DT(*kept, at::kInt); CHECK_CONTIG(*kept);
+    TORCH_CHECK(kept->numel() == rows, "kept shape");
+  }
+  const c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
+  RC(oamd::sample_threshold(logits.data_ptr(), logits.scalar_type() == at::kBFloat16, logits.stride(0), (int)rows,
+                            (int)logits.size(1), ptr<float>(temperature), ptr<int>(top_k), ptr<float>(top_p),
+                            ptr<float>(thr), optr<int>(kept), cur_stream()));
 }
 
 }  // namespace
@@ -701,7 +726,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("attn_prefill_block_q", &oamd::attn_prefill_block_q);
   m.def("sample", &sample, pybind11::arg("logits"), pybind11::arg("temperature"), pybind11::arg("seeds"),
         pybind11::arg("positions"), pybind11::arg("out"), pybind11::arg("col_offset") = 0,
-        pybind11::arg("out_val") = pybind11::none());
+        pybind11::arg("out_val") = pybind11::none(), pybind11::arg("thr") = pybind11::none());
+  m.def("sample_threshold", &sample_threshold, pybind11::arg("logits"), pybind11::arg("temperature"),
+        pybind11::arg("top_k"), pybind11::arg("top_p"), pybind11::arg("thr"), pybind11::arg("kept") = pybind11::none());
   m.def("graph_launch", &graph_launch, pybind11::arg("graph_exec"), pybind11::arg("count"), pybind11::arg("stream"));
   register_scan_bindings(m);
   register_comm_bindings(m);

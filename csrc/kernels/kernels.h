@@ -124,7 +124,14 @@ int attn_prefill(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* o, c
                  const bf16_t* pk = nullptr, const bf16_t* pv = nullptr, const int* seq_pfx = nullptr);
 int sample_tokens(const void* logits, bool logits_bf16, int64_t stride, int rows, int vocab,
                   const float* temperature, const int64_t* seeds, const int64_t* positions,
-                  int64_t* out_tokens, int64_t col_offset, float* out_val, hipStream_t stream);
+                  int64_t* out_tokens, int64_t col_offset, float* out_val, hipStream_t stream,
+                  const float* thr = nullptr);
+// Top-k / top-p as one threshold per row (sample.hip): thr[row] = the smallest kept logit value,
+// -inf for a greedy or unfiltered row (decided before any logit is read); sample_tokens given
+// `thr` samples among the columns with logit >= thr[row]. kept (optional): their number.
+int sample_threshold(const void* logits, bool logits_bf16, int64_t stride, int rows, int vocab,
+                     const float* temperature, const int* top_k, const float* top_p, float* thr, int* kept,
+                     hipStream_t stream);
 
 // One-shot all-reduce over peer-mapped fine-grained buffers (allreduce.hip).
 size_t car_buffer_bytes(size_t cap_bytes, int world);

@@ -79,7 +79,12 @@ def cmd_explain(args) -> int:
     ee = ExplainEngine(llm, tok, model_id=s.engine.model, max_prompt_tokens=s.engine.max_prompt_tokens)
     docs = [open(p, "rb").read() for p in args.logs]
     res = eng.analyze(docs, [(os.path.basename(p), None) for p in args.logs])
-    cfg = AIProviderConfig(max_tokens=args.max_tokens, temperature=args.temperature)
+    extra = {}
+    if args.top_k:
+        extra["top_k"] = str(args.top_k)
+    if args.top_p is not None and args.top_p != 1.0:
+        extra["top_p"] = str(args.top_p)
+    cfg = AIProviderConfig(max_tokens=args.max_tokens, temperature=args.temperature, additional_headers=extra or None)
     outs = ee.explain_many([(r, cfg) for r in res])
     print(json.dumps([o.to_obj() if hasattr(o, "to_obj") else {"error": str(o)} for o in outs], indent=1))
     ee.close()
@@ -355,6 +360,9 @@ def main(argv: list[str] | None = None) -> int:
     p.add_argument("--patterns", action="append")
     p.add_argument("--max-tokens", type=int, default=500)
     p.add_argument("--temperature", type=float, default=0.3)
+    p.add_argument("--top-k", type=int, default=0, help="sample among the k most likely tokens (0 = off)")
+    p.add_argument("--top-p", type=float, default=1.0,
+                   help="nucleus sampling: the smallest set of tokens holding this probability (1 = off)")
     p = sub.add_parser("serve-compat")
     common(p)
     p.add_argument("--patterns", action="append")

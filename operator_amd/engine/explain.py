@@ -11,6 +11,9 @@ caching on / 500 tokens / T=0.3 per AIInterfaceClient.java:78-84):
 * ``timeoutSeconds`` -> per-attempt deadline; the request is cancelled (its KV
                         pages freed) and retried up to ``maxRetries`` times
 * ``cachingEnabled`` -> LRU of responses keyed by (model, prompt, T, maxTokens)
+* ``additionalConfig`` -> ``top_k`` / ``top_p`` (string values, "Provider specific settings";
+                        the CRD has no field of its own for them): top-k / nucleus sampling
+                        of the on-node engine, part of the cache key when set
 * ``promptTemplate`` -> operator_amd.engine.prompt.render
 
 Requests from any number of threads are batched continuously by one engine
@@ -254,9 +257,30 @@ class ExplainEngine:
             return prompt_mod.render_bounded_batch([(r, c.prompt_template) for r, c in items], self.tok,
                                                    self.max_prompt_tokens)
 
+    @staticmethod
+    def _filters(cfg: AIProviderConfig) -> tuple[int, float]:
+        """(top_k, top_p) of an AIProvider's ``additionalConfig`` (string values; absent = off)."""
+        extra = cfg.additional_headers or {}
+        top_k, top_p = 0, 1.0
+        try:
+            if extra.get("top_k") is not None:
+                top_k = int(str(extra["top_k"]).strip())
+            if extra.get("top_p") is not None:
+                top_p = float(str(extra["top_p"]).strip())
+        except ValueError:
+            raise ExplainError(f"additionalConfig top_k / top_p: not a number "
+                               f"(top_k={extra.get('top_k')!r}, top_p={extra.get('top_p')!r})") from None
+        if not 0 <= top_k < 2 ** 31 or not 0 < top_p <= 1:
+            raise ExplainError(f"additionalConfig: top_k must be >= 0 and top_p in (0, 1], got "
+                               f"top_k={top_k}, top_p={top_p}")
+        return top_k, top_p
+
     def _key(self, ids: list[int], cfg: AIProviderConfig) -> str:
         h = hashlib.sha256()
         h.update(f"{cfg.model_id}|{cfg.temperature}|{cfg.max_tokens}|".encode())
+        top_k, top_p = self._filters(cfg)
+        if top_k > 0 or top_p < 1:   # only when set: the keys of every other provider stay as they were
+            h.update(f"top_k={top_k}|top_p={top_p}|".encode())
         h.update(bytes(str(ids), "ascii"))
         return h.hexdigest()
 
@@ -290,8 +314,9 @@ class ExplainEngine:
 
     def _start(self, p: _Pending, ids: list[int], notify: bool = True) -> None:
         cfg = p.cfg
+        top_k, top_p = self._filters(cfg)
         p.req = GenRequest(ids, max_tokens=max(1, int(cfg.max_tokens)), temperature=float(cfg.temperature),
-                           seed=self._seed(ids) + p.attempt, ignore_eos=self.ignore_eos)
+                           seed=self._seed(ids) + p.attempt, ignore_eos=self.ignore_eos, top_k=top_k, top_p=top_p)
         self.llm.submit(p.req)
         if notify:
             self.loop.notify()
@@ -387,12 +412,14 @@ class ExplainEngine:
 
     # ------------------------------------------------------------------ raw completions
     def complete(self, ids: list[int], max_tokens: int = 500, temperature: float = 0.3, seed: int | None = None,
-                 timeout_s: float | None = None) -> dict:
+                 timeout_s: float | None = None, top_k: int = 0, top_p: float = 1.0) -> dict:
         """Generate from raw prompt token ids on the same continuous batch as the
-        explanations (the OpenAI / Ollama endpoints of engine/server.py). Raises
-        ExplainError on a timeout, an engine error or a prompt the engine cannot hold."""
+        explanations (the OpenAI / Ollama endpoints of engine/server.py). ``top_k`` (0 = off) /
+        ``top_p`` (1 = off): top-k / nucleus sampling. Raises ExplainError on a timeout, an
+        engine error, a prompt the engine cannot hold or sampling parameters it rejects."""
         req = GenRequest(list(ids), max_tokens=max(1, int(max_tokens)), temperature=max(0.0, float(temperature)),
-                         seed=self._seed(ids) if seed is None else int(seed), ignore_eos=self.ignore_eos)
+                         seed=self._seed(ids) if seed is None else int(seed), ignore_eos=self.ignore_eos,
+                         top_k=top_k, top_p=top_p)
         want = req.max_tokens
         t0 = time.perf_counter()
         try:

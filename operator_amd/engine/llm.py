@@ -53,6 +53,8 @@ class GenRequest:
     temperature: float = 0.3
     seed: int = 0
     ignore_eos: bool = False
+    top_k: int = 0          # sample among the k most likely tokens (0 = off)
+    top_p: float = 1.0      # ... among the smallest set of them holding this much probability (1 = off)
     rid: int = -1
     # runtime state
     pages: list[int] = field(default_factory=list)
@@ -166,7 +168,7 @@ class _BucketState:
         mp = eng.max_pages
         self._spec = (("step", (1,), torch.long), ("ids", (bp,), torch.long), ("pos", (bp,), torch.long),
                       ("seeds", (bp,), torch.long), ("ctx", (bp,), torch.int32), ("temp", (bp,), torch.float32),
-                      ("bt", (bp, mp), torch.int32))
+                      ("topk", (bp,), torch.int32), ("topp", (bp,), torch.float32), ("bt", (bp, mp), torch.int32))
         self._nbytes = sum(int(np.prod(s)) * torch.empty((), dtype=dt).element_size() for _, s, dt in self._spec)
         self._buf = torch.zeros(self._nbytes, dtype=torch.uint8, device=dev)
         for n, t in self._views(self._buf).items():
@@ -179,6 +181,7 @@ class _BucketState:
         self.step_host = 0
         self.slots = torch.zeros(bp, dtype=torch.long, device=dev)   # per step: cache slot of each row's token
         self.spos = torch.zeros(bp, dtype=torch.long, device=dev)    # per step: sampler stream position
+        self.thr = torch.zeros(bp, dtype=torch.float32, device=dev)  # per step: top-k / top-p threshold of each row
 
     def _views(self, buf: torch.Tensor) -> dict:
         out, off = {}, 0
@@ -197,6 +200,7 @@ class _BucketState:
         v = {k: t.numpy() for k, t in self._views(host).items()}
         ids, pos, ctx, bt, temp, seeds = v["ids"], v["pos"], v["ctx"], v["bt"], v["temp"], v["seeds"]
         assert bt.shape[1] == max_pages
+        v["topp"][:] = 1.0   # padding rows: unfiltered (topk 0)
         if n:
             lens = np.fromiter((r.length for r in reqs), dtype=np.int64, count=n)
             ids[:n] = np.fromiter((r.output[-1] for r in reqs), dtype=np.int64, count=n)
@@ -204,6 +208,8 @@ class _BucketState:
             ctx[:n] = lens
             temp[:n] = np.fromiter((r.temperature for r in reqs), dtype=np.float32, count=n)
             seeds[:n] = np.fromiter((r.seed for r in reqs), dtype=np.int64, count=n)
+            v["topk"][:n] = np.fromiter((r.top_k for r in reqs), dtype=np.int32, count=n)
+            v["topp"][:n] = np.fromiter((r.top_p for r in reqs), dtype=np.float32, count=n)
             for i, r in enumerate(reqs):
                 bt[i, :len(r.pages)] = r.pages
         nb = self._buf.is_cuda
@@ -252,7 +258,9 @@ class _DecodeGraph:
         fb = ForwardBatch(st.ids, st.pos, slots, False, None, block_tables=st.bt, context_lens=st.ctx,
                           num_splits=self.splits)
         logits = e.model.forward(fb, e.kv)
-        tok = e.model.sample(logits, st.temp, st.seeds, spos)
+        # threshold kernel + filtered sampler in every graph: rows at the defaults (top_k 0,
+        # top_p 1) leave the first at once with thr = -inf and sample as before
+        tok = e.model.sample(logits, st.temp, st.seeds, spos, top_k=st.topk, top_p=st.topp, thr=st.thr)
         if gpu:
             ops.kernels().decode_advance(tok, st.ids, st.hist, st.pos, st.ctx, st.step)
         else:
@@ -315,7 +323,7 @@ class _PrefillGraph:
         # profiles/bench_r4_flagship_idle.jsonl "copyBuffer -> copyBuffer")
         spec = (("ids", T, i64), ("pos", T, i64), ("slots", T, i64), ("last", S, i64), ("seeds", S, i64),
                 ("spos", S, i64), ("cu", S + 1, i32), ("ws", self.W, i32), ("wq", self.W, i32),
-                ("temp", S, torch.float32), ("pfx", S, i32))
+                ("temp", S, torch.float32), ("pfx", S, i32), ("topk", S, i32), ("topp", S, torch.float32))
         self._layout, off = [], 0
         for n, k, dt in spec:
             isz = torch.empty((), dtype=dt).element_size()
@@ -324,6 +332,7 @@ class _PrefillGraph:
         self._nbytes = off
         self._dbuf = torch.zeros(off, dtype=torch.uint8, device=dev)
         self.dev = self._views(self._dbuf)
+        self.thr = torch.zeros(S, dtype=torch.float32, device=dev)   # top-k / top-p threshold of each first token
         # two pinned input sets + sampled-token buffers, used alternately: a launch
         # returns without waiting for the GPU, so the engine can queue the next
         # prefill batch before reading this one's tokens (LLMEngine._prefill); a set is
@@ -349,7 +358,8 @@ class _PrefillGraph:
         fb = ForwardBatch(d["ids"], d["pos"], d["slots"], True, d["last"], seq_lens=[],
                           prefill_work=(d["cu"], d["ws"], d["wq"], self.variant), prefix=pre)
         logits = e.model.forward(fb, e.kv)
-        self.tok = e.model.sample(logits, d["temp"], d["seeds"], d["spos"])
+        self.tok = e.model.sample(logits, d["temp"], d["seeds"], d["spos"], top_k=d["topk"], top_p=d["topp"],
+                                  thr=self.thr)
 
     def capture(self, pool) -> None:
         # every work item padding and every slot -1 while warming up: no KV writes
@@ -366,7 +376,7 @@ class _PrefillGraph:
             self._run()
         self.graph = g
 
-    def launch(self, ids, pos, slots, cu, ws, wq, last, temp, seeds, spos, pfx=None):
+    def launch(self, ids, pos, slots, cu, ws, wq, last, temp, seeds, spos, pfx=None, topk=None, topp=None):
         """Queue one replay for the real batch (numpy inputs, <= T tokens, <= S
         sequences); returns (pinned token buffer, event): ``event`` completes when the
         batch's sampled first tokens are in the buffer."""
@@ -378,7 +388,9 @@ class _PrefillGraph:
         b = len(last)
         for name, arr, fill in (("ids", ids, 0), ("pos", pos, 0), ("slots", slots, -1), ("last", last, 0),
                                 ("seeds", seeds, 0), ("spos", spos, 0), ("temp", temp, 0.0), ("ws", ws, -1),
-                                ("wq", wq, 0), ("cu", cu, int(cu[-1])), ("pfx", pfx if pfx is not None else [], 0)):
+                                ("wq", wq, 0), ("cu", cu, int(cu[-1])), ("pfx", pfx if pfx is not None else [], 0),
+                                ("topk", topk if topk is not None else [], 0),
+                                ("topp", topp if topp is not None else [], 1.0)):
             v = h[name].numpy()
             v[:len(arr)] = arr
             v[len(arr):] = fill
@@ -509,9 +521,21 @@ class LLMEngine:
             self._pv = torch.zeros(shape, dtype=torch.bfloat16, device=self.device)
 
     # ------------------------------------------------------------------ API
+    def check_sampling(self, req: GenRequest) -> None:
+        """ValueError for top_k / top_p out of range, or set on a tensor-parallel replica (the
+        vocabulary is sharded there and no collective computes the global threshold)."""
+        k, p = req.top_k, req.top_p
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= k < 2 ** 31:
+            raise ValueError(f"top_k must be an integer >= 0 (0 = off), got {k!r}")
+        if isinstance(p, bool) or not isinstance(p, (int, float, np.floating)) or not 0 < p <= 1:
+            raise ValueError(f"top_p must be in (0, 1] (1 = off), got {p!r}")
+        if (k > 0 or p < 1) and self.model.tp.world > 1:
+            raise ValueError("top_k / top_p are not supported with engine.tp > 1")
+
     def submit(self, req: GenRequest) -> GenRequest:
         if not req.prompt:
             raise ValueError("empty prompt")
+        self.check_sampling(req)
         if len(req.prompt) + req.max_tokens > self.max_context:
             req.max_tokens = max(1, self.max_context - len(req.prompt))
             if len(req.prompt) >= self.max_context:
@@ -838,9 +862,11 @@ class LLMEngine:
         ws, wq = ops.prefill_work_list(lens, ops.prefill_block_q(self.model.hq, self.model.hkv, var))
         temps = [r.temperature for r in batch]
         seeds = [r.seed for r in batch]
+        topk = [r.top_k for r in batch]
+        topp = [r.top_p for r in batch]
         g = self._prefill_graph_for(len(ids), len(batch))
         if g is not None:
-            toks, ev = g.launch(ids, pos, slots, cu, ws, wq, last, temps, seeds, full, skip)
+            toks, ev = g.launch(ids, pos, slots, cu, ws, wq, last, temps, seeds, full, skip, topk, topp)
             self.stats.prefill_graph_replays += 1
             self.stats.prefill_padded_tokens += g.T - len(ids)
         else:
@@ -850,7 +876,8 @@ class LLMEngine:
             pre = None if pfx is None else (self._pk, self._pv, t(pfx, torch.int32), pfx)
             fb = ForwardBatch(t(ids), t(pos), t(slots), True, t(last), seq_lens=lens, prefill_work=work, prefix=pre)
             logits = self.model.forward(fb, self.kv)
-            tk = self.model.sample(logits, t(temps, torch.float32), t(seeds), t(full))
+            tk = self.model.sample(logits, t(temps, torch.float32), t(seeds), t(full), top_k=t(topk, torch.int32),
+                                   top_p=t(topp, torch.float32))
             if dev.type == "cuda":
                 toks = torch.empty(len(batch), dtype=torch.long, pin_memory=True)
                 toks.copy_(tk, non_blocking=True)

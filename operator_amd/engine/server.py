@@ -41,9 +41,24 @@ class BadRequest(ValueError):
     pass
 
 
+def _top_k(v) -> int:
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 <= v < 2 ** 31 or v != int(v):
+        raise ValueError(f"top_k must be an integer >= 0, got {v!r}")
+    return int(v)
+
+
+def _top_p(v) -> float:
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 < v <= 1:
+        raise ValueError(f"top_p must be a number in (0, 1], got {v!r}")
+    return float(v)
+
+
 def _sampling(body: dict, ollama: bool) -> dict:
-    """max_tokens / temperature / seed of an OpenAI body or an Ollama ``options`` map
-    (defaults: the AIProvider CRD's 500 tokens at T = 0.3)."""
+    """max_tokens / temperature / seed / top_k / top_p of an OpenAI body or an Ollama
+    ``options`` map (defaults: the AIProvider CRD's 500 tokens at T = 0.3). ``top_p`` is part
+    of the OpenAI body and ``top_k`` the extension vLLM-compatible clients send; both are
+    standard Ollama options. Absent or null means off: an Ollama server applies top_k 40 /
+    top_p 0.9 to a request that names neither, this one does not (docs/PARITY.md)."""
     src = (body.get("options") or {}) if ollama else body
     if not isinstance(src, dict):
         raise BadRequest("'options' must be an object")
@@ -53,6 +68,10 @@ def _sampling(body: dict, ollama: bool) -> dict:
               "temperature": float(src.get("temperature", 0.3)), "timeout_s": COMPLETION_TIMEOUT_S}
         if src.get("seed") is not None:
             kw["seed"] = int(src["seed"])
+        if src.get("top_k") is not None:
+            kw["top_k"] = _top_k(src["top_k"])
+        if src.get("top_p") is not None:
+            kw["top_p"] = _top_p(src["top_p"])
         n_choices = int(body.get("n", 1) or 1)
     except (TypeError, ValueError) as e:
         raise BadRequest(f"bad sampling parameter: {e}") from None
@@ -182,7 +201,7 @@ class CompatServer:
                     return self._send(400, {"error": {"message": str(e), "type": "invalid_request_error"}})
                 except Exception as e:  # noqa: BLE001
                     msg = str(e)
-                    if "exceeds max_context" in msg:
+                    if "exceeds max_context" in msg or "top_k / top_p are not supported" in msg:
                         return self._send(400, {"error": {"message": msg, "type": "invalid_request_error"}})
                     log.error("request %s failed: %s", self.path, e)
                     return self._send(504 if "timed out" in msg else 500, {"error": {"message": msg}})

@@ -88,6 +88,7 @@ class TPLLMEngine(LLMEngine):
             raise RuntimeError("requests are submitted to the TP leader (rank 0) only")
         if not req.prompt:
             raise ValueError("empty prompt")
+        self.check_sampling(req)   # before the broadcast: every rank sees the same decision
         if len(req.prompt) >= self.max_context:
             raise ValueError(f"prompt of {len(req.prompt)} tokens exceeds max_context {self.max_context}")
         with self._qlock:

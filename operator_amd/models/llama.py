@@ -289,11 +289,17 @@ class LlamaModel:
         return ops.linear(x, self.lm_head)
 
     def sample(self, logits: torch.Tensor, temperature: torch.Tensor, seeds: torch.Tensor,
-               positions: torch.Tensor) -> torch.Tensor:
+               positions: torch.Tensor, top_k: torch.Tensor | None = None, top_p: torch.Tensor | None = None,
+               thr: torch.Tensor | None = None) -> torch.Tensor:
         """Sample one token per row; under TP each rank samples its vocab shard and the
-        global winner is the max perturbed value (ties -> smaller token id)."""
+        global winner is the max perturbed value (ties -> smaller token id).
+
+        ``top_k`` / ``top_p`` (per row; ``thr``: the threshold buffer, ops.sample) filter the
+        candidates at tp.world == 1. A vocab shard cannot compute the global threshold, so
+        under TP they are not applied: the engine admits no filtered request there
+        (LLMEngine.submit)."""
         if self.tp.world == 1:
-            return ops.sample(logits, temperature, seeds, positions)
+            return ops.sample(logits, temperature, seeds, positions, top_k=top_k, top_p=top_p, thr=thr)
         n = logits.shape[0]
         val = torch.empty(n, dtype=torch.float32, device=logits.device)
         tok = ops.sample(logits, temperature, seeds, positions, col_offset=self.vocab_offset, out_val=val)

@@ -17,6 +17,7 @@ from ._native import kernels, native_available, patterns
 
 __all__ = [
     "rmsnorm", "silu_mul", "embedding", "rope_kv", "attn_prefill", "attn_decode", "attn_decode_rope", "sample",
+    "sample_threshold",
     "kernels", "patterns", "native_available", "reference", "prefill_work_list", "prefill_block_q", "prefill_variant", "decode_splits",
     "decode_workspace", "linear", "gemm_splits", "gemm_plan", "gate_up_silu", "interleave_gate_up",
     "quantize_fp8", "silu_quantize_fp8", "linear_fp8", "fp8_plan", "SplitK", "linear_tile", "tile_ok", "BLAS_CALLS",
@@ -671,21 +672,62 @@ def attn_decode_rope(qkv, pos: torch.Tensor, cos: torch.Tensor, sin: torch.Tenso
     return (q8, sx) if quant else o
 
 
+def sample_threshold(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor,
+                     out: torch.Tensor | None = None, out_kept: torch.Tensor | None = None) -> torch.Tensor:
+    """Top-k / top-p as one fp32 threshold per row: the candidates of row r are the columns
+    with logit >= thr[r] (semantics: ``reference.sample_threshold``). ``top_k`` int32 (0 = off),
+    ``top_p`` fp32 (1 = off); greedy rows and rows with both off get -inf without their logits
+    being read. ``out_kept`` (int32) receives the number of candidates."""
+    rows = logits.shape[0]
+    if not logits.is_cuda:
+        thr, kept = reference.sample_threshold(logits, temperature, top_k, top_p)
+        if out_kept is not None:
+            out_kept.copy_(kept)
+        if out is not None:
+            out.copy_(thr)
+            return out
+        return thr
+    o = out if out is not None else torch.empty(rows, dtype=torch.float32, device=logits.device)
+    kernels().sample_threshold(logits, temperature, top_k, top_p, o, out_kept)
+    return o
+
+
 def sample(logits: torch.Tensor, temperature: torch.Tensor, seeds: torch.Tensor, positions: torch.Tensor,
-           out: torch.Tensor | None = None, col_offset: int = 0, out_val: torch.Tensor | None = None) -> torch.Tensor:
+           out: torch.Tensor | None = None, col_offset: int = 0, out_val: torch.Tensor | None = None,
+           top_k: torch.Tensor | None = None, top_p: torch.Tensor | None = None,
+           thr: torch.Tensor | None = None) -> torch.Tensor:
     """Temperature / Gumbel-max sampling (greedy rows where temperature <= 0).
 
     For a vocab shard pass ``col_offset`` (global id of column 0) and ``out_val``
     (receives each row's winning perturbed value) and take the max over shards.
+
+    ``top_k`` (int32, 0 = off) / ``top_p`` (fp32, 1 = off), one per row: ``sample_threshold``
+    into ``thr`` (a buffer of the caller's, for graph capture, or a fresh one), then the sampler
+    restricted to the columns with logit >= thr[row]. With ``thr`` alone the sampler is
+    restricted by the thresholds the caller computed; that is the only filtered form a vocab
+    shard can use (its own logits cannot give the global threshold), so ``top_k`` / ``top_p``
+    with a ``col_offset`` raise.
     """
+    rows = logits.shape[0]
+    if top_k is not None or top_p is not None:
+        if col_offset != 0:
+            raise ValueError("top_k / top_p on a vocab shard (col_offset != 0) need a global threshold: pass thr")
+        if top_k is None:
+            top_k = torch.zeros(rows, dtype=torch.int32, device=logits.device)
+        if top_p is None:
+            top_p = torch.ones(rows, dtype=torch.float32, device=logits.device)
+        thr = sample_threshold(logits, temperature, top_k, top_p, out=thr)
     if not logits.is_cuda:
-        tok, val = reference.sample_shard(logits, temperature, seeds, positions, col_offset)
+        tok, val = reference.sample_shard(logits, temperature, seeds, positions, col_offset, thr=thr)
         if out_val is not None:
             out_val.copy_(val)
         if out is not None:
             out.copy_(tok)
             return out
         return tok
-    o = out if out is not None else torch.empty(logits.shape[0], dtype=torch.long, device=logits.device)
-    kernels().sample(logits, temperature, seeds, positions, o, col_offset, out_val)
+    o = out if out is not None else torch.empty(rows, dtype=torch.long, device=logits.device)
+    if thr is None:
+        kernels().sample(logits, temperature, seeds, positions, o, col_offset, out_val)
+    else:
+        kernels().sample(logits, temperature, seeds, positions, o, col_offset, out_val, thr)
     return o

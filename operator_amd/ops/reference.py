@@ -223,19 +223,73 @@ def gumbel_noise_ref(seed: int, position: int, vocab: int, col_offset: int = 0) 
     return -torch.log(-torch.log(u))
 
 
+def sample_threshold(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor,
+                     top_p: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """Top-k / top-p as one threshold per row, fp64 and sort-based: (thr fp32, kept int32),
+    the candidate set of row r being the columns with logit >= thr[r] (docs/PARITY.md "Sampling").
+
+    * greedy rows (T <= 0) and rows with both filters off (top_k <= 0 or >= vocab; top_p >= 1):
+      thr = -inf, kept = vocab;
+    * tau_k = the top_k-th largest logit, ties at it all kept (HF TopKLogitsWarper);
+    * m(v) = sum of exp((x - max) / T) over kept x >= v; tau_p = the largest logit v with
+      m(v) >= top_p * m(tau_k): top-p after temperature, over the top-k survivors;
+    * thr = max(tau_k, tau_p). NaN logits are never kept, -0 and +0 are one value, -inf
+      logits carry mass 0.
+    """
+    rows, V = logits.shape
+    thr = torch.full((rows,), float("-inf"), dtype=torch.float32)
+    kept = torch.full((rows,), V, dtype=torch.int32)
+    for r in range(rows):
+        t, k, p = float(temperature[r]), int(top_k[r]), float(top_p[r])
+        use_k, use_p = 0 < k < V, p < 1
+        if not t > 0 or not (use_k or use_p):
+            continue
+        x = logits[r].double().cpu()
+        s = torch.sort(x[~torch.isnan(x)], descending=True).values + 0.0   # + 0.0: -0 -> +0
+        n = s.numel()
+        if n == 0 or s[0] == float("-inf"):   # every mass is 0: nothing to cut
+            kept[r] = n
+            continue
+        if use_k:
+            s = s[s >= s[min(k, n) - 1]]
+        tau, cnt = s[-1], s.numel()
+        if use_p:
+            w = torch.exp((s - s[0]) / t)
+            w[s == s[0]] = 1.0                # also for max = +inf (inf - inf)
+            c = torch.cumsum(torch.nan_to_num(w, nan=0.0), 0)
+            vals, counts = torch.unique_consecutive(s, return_counts=True)
+            ends = torch.cumsum(counts, 0) - 1
+            j = int(torch.nonzero(c[ends] >= max(p, 0.0) * c[-1])[0])
+            tau, cnt = vals[j], int(ends[j]) + 1
+        thr[r] = float(tau)
+        kept[r] = cnt
+    return thr.to(logits.device), kept.to(logits.device)
+
+
 def sample_shard(logits: torch.Tensor, temperature: torch.Tensor, seeds: torch.Tensor, positions: torch.Tensor,
-                 col_offset: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
-    """Greedy when T<=0 else Gumbel-max with the same counter hash as the kernel.
+                 col_offset: int = 0, top_k: torch.Tensor | None = None, top_p: torch.Tensor | None = None,
+                 thr: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """Greedy when T<=0 else Gumbel-max with the same counter hash as the kernel, over the
+    columns with logit >= the row's threshold when ``top_k`` / ``top_p`` (``sample_threshold``;
+    either may be None = off) or a precomputed ``thr`` is given.
 
     Returns (global token ids, winning perturbed values) for a vocab shard.
     """
-    out = torch.empty(logits.shape[0], dtype=torch.long)
-    val = torch.empty(logits.shape[0], dtype=torch.float32)
-    for r in range(logits.shape[0]):
+    rows = logits.shape[0]
+    if top_k is not None or top_p is not None:
+        top_k = torch.zeros(rows, dtype=torch.int32) if top_k is None else top_k
+        top_p = torch.ones(rows, dtype=torch.float32) if top_p is None else top_p
+        thr = sample_threshold(logits, temperature, top_k, top_p)[0]
+    out = torch.empty(rows, dtype=torch.long)
+    val = torch.empty(rows, dtype=torch.float32)
+    for r in range(rows):
         x = logits[r].double().cpu()
         t = float(temperature[r])
+        cut = x < float(thr[r]) if thr is not None else None
         if t > 0:
             x = x / t + gumbel_noise_ref(int(seeds[r]), int(positions[r]), x.numel(), col_offset)
+        if cut is not None and bool(cut.any()):
+            x = x.masked_fill(cut, float("-inf"))
         i = int(torch.argmax(x))
         out[r] = i + col_offset
         val[r] = float(x[i])
