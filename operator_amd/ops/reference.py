@@ -183,8 +183,8 @@ def attn_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, b
     G = Hq // Hkv
     out = torch.zeros_like(q)
     for b in range(B):
-        L = int(seq_lens[b])
-        if L == 0:
+        L = min(int(seq_lens[b]), block_tables.shape[1] * P)   # a length above the table's capacity is clamped
+        if L <= 0:
             continue
         npg = (L + P - 1) // P
         pages = block_tables[b, :npg].long()
