@@ -213,34 +213,44 @@ void rope_kv(const at::Tensor& qkv, const at::Tensor& pos, const at::Tensor& cos
                    xp, (int)splits, optr<bf16_t>(bias), fp8, (float)k_scale, (float)v_scale, cur_stream()));
 }
 
+// y / p of the split-K decode GEMMs (gemm_decode, gemm_pp, gemm_w4, gemm_skinny) as raw pointers: y [M, N]
+// (N / 2 with the SwiGLU epilogue) may be omitted only where the consumer sums the fp32 slabs (splits > 1, no
+// SwiGLU); splits > 1 needs a contiguous fp32 p of at least splits * M * N.
+std::pair<bf16_t*, float*> gemm_outputs(const c10::optional<at::Tensor>& y_opt, const c10::optional<at::Tensor>& p_opt,
+                                        int64_t M, int64_t N, int64_t splits, bool silu_gu) {
+  bf16_t* yp = nullptr;
+  if (y_opt.has_value()) {
+    const at::Tensor& y = *y_opt;
+    CHECK_DEV(y); CHECK_BF16(y); CHECK_CONTIG(y);
+    TORCH_CHECK(y.dim() == 2 && y.size(0) == M && y.size(1) == (silu_gu ? N / 2 : N), "gemm shapes: y [M, N] (N / 2 with silu_gu)");
+    yp = ptr<bf16_t>(y);
+  } else {
+    TORCH_CHECK(splits > 1 && !silu_gu, "y may be omitted only for split-K slabs summed by the consumer");
+  }
+  float* pp = nullptr;
+  if (splits > 1) {
+    TORCH_CHECK(p_opt.has_value(), "split-K needs a partial buffer");
+    const at::Tensor& p = *p_opt;
+    CHECK_DEV(p); CHECK_DT(p, at::kFloat); CHECK_CONTIG(p);
+    TORCH_CHECK(p.numel() >= splits * M * N, "partial buffer too small");
+    pp = p.data_ptr<float>();
+  }
+  return {yp, pp};
+}
+
 void gemm_decode(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& y_opt,
                  const c10::optional<at::Tensor>& p,
                  int64_t splits, int64_t bn, int64_t bm, bool silu_gu, bool w_tiled, int64_t stages) {
   CHECK_DEV(x); CHECK_BF16(x); CHECK_BF16(w); CHECK_CONTIG(x); CHECK_CONTIG(w);
   TORCH_CHECK(x.dim() == 2 && w.dim() == 2, "x [M,K], w [N,K]");
   const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
-  bf16_t* yp = nullptr;
-  if (y_opt.has_value()) {
-    const at::Tensor& y = *y_opt;
-    CHECK_BF16(y); CHECK_CONTIG(y);
-    TORCH_CHECK(y.dim() == 2 && y.size(0) == M && y.size(1) == (silu_gu ? N / 2 : N), "gemm shapes");
-    yp = ptr<bf16_t>(y);
-  } else {
-    TORCH_CHECK(splits > 1 && !silu_gu, "y may be omitted only for split-K slabs summed by the consumer");
-  }
   TORCH_CHECK(w.size(1) == K, "gemm shapes (a tiled w keeps its logical [N, K] shape)");
   TORCH_CHECK(!silu_gu || (bn == 128 && splits == 1), "fused SwiGLU needs bn = 128, splits = 1");
   if (bm == 0) bm = std::min<int64_t>(M, 256);
   TORCH_CHECK((bm == 64 || bm == 128 || bm == 256) && M % bm == 0, "gemm_decode: M % bm, bm in {64,128,256}");
   TORCH_CHECK((bn == 64 || bn == 128) && N % bn == 0, "gemm_decode: N % bn, bn in {64, 128}");
   TORCH_CHECK(splits >= 1 && splits <= 16 && K % 64 == 0 && K / 64 >= splits, "gemm_decode: bad split count");
-  float* pp = nullptr;
-  if (splits > 1) {
-    TORCH_CHECK(p.has_value(), "split-K needs a partial buffer");
-    CHECK_DT(*p, at::kFloat); CHECK_CONTIG(*p);
-    TORCH_CHECK(p->numel() >= splits * M * N, "partial buffer too small");
-    pp = p->data_ptr<float>();
-  }
+  const auto [yp, pp] = gemm_outputs(y_opt, p, M, N, splits, silu_gu);
   TORCH_CHECK(K < (1LL << 31) / 64 && M * K < (1LL << 31) && N * K < (1LL << 40), "gemm too large");
   const c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
   RC(oamd::gemm_decode(ptr<bf16_t>(x), ptr<bf16_t>(w), yp, pp, (int)M, (int)N, (int)K, (int)splits,
@@ -300,21 +310,7 @@ void gemm_pp(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::T
   TORCH_CHECK(bm == 128 || bm == 256, "gemm_pp: bm in {128, 256}");
   TORCH_CHECK(splits >= 1 && splits <= 32 && K % (64 * splits) == 0, "gemm_pp: K % (64 * splits) == 0");
   TORCH_CHECK(!silu_gu || splits == 1, "gemm_pp: fused SwiGLU needs splits == 1");
-  bf16_t* yp = nullptr;
-  if (y_opt.has_value()) {
-    CHECK_BF16(*y_opt); CHECK_CONTIG(*y_opt);
-    TORCH_CHECK(y_opt->dim() == 2 && y_opt->size(0) == M && y_opt->size(1) == (silu_gu ? N / 2 : N), "gemm_pp: y");
-    yp = ptr<bf16_t>(*y_opt);
-  } else {
-    TORCH_CHECK(splits > 1 && !silu_gu, "y may be omitted only for split-K slabs summed by the consumer");
-  }
-  float* pp = nullptr;
-  if (splits > 1) {
-    TORCH_CHECK(p.has_value(), "split-K needs a partial buffer");
-    CHECK_DT(*p, at::kFloat); CHECK_CONTIG(*p);
-    TORCH_CHECK(p->numel() >= splits * M * N, "partial buffer too small");
-    pp = p->data_ptr<float>();
-  }
+  const auto [yp, pp] = gemm_outputs(y_opt, p, M, N, splits, silu_gu);
   TORCH_CHECK(M * K < (1LL << 40) && N * K < (1LL << 40), "gemm too large");
   const c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
   float* wsp = nullptr;
@@ -341,21 +337,7 @@ void gemm_w4(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::T
   TORCH_CHECK(K >= 64 && K % 64 == 0 && K < (1LL << 22), "gemm_w4: K % 64 == 0, K < 2^22");
   TORCH_CHECK(splits >= 1 && splits <= 16 && splits <= K / 64, "gemm_w4: 1 <= splits <= min(16, K / 64)");
   TORCH_CHECK(!silu_gu || splits == 1, "gemm_w4: fused SwiGLU needs splits == 1");
-  bf16_t* yp = nullptr;
-  if (y_opt.has_value()) {
-    CHECK_DEV(*y_opt); CHECK_BF16(*y_opt); CHECK_CONTIG(*y_opt);
-    TORCH_CHECK(y_opt->dim() == 2 && y_opt->size(0) == M && y_opt->size(1) == (silu_gu ? N / 2 : N), "gemm_w4: y");
-    yp = ptr<bf16_t>(*y_opt);
-  } else {
-    TORCH_CHECK(splits > 1 && !silu_gu, "y may be omitted only for split-K slabs summed by the consumer");
-  }
-  float* pp = nullptr;
-  if (splits > 1) {
-    TORCH_CHECK(p.has_value(), "split-K needs a partial buffer");
-    CHECK_DEV(*p); CHECK_DT(*p, at::kFloat); CHECK_CONTIG(*p);
-    TORCH_CHECK(p->numel() >= splits * M * N, "partial buffer too small");
-    pp = p->data_ptr<float>();
-  }
+  const auto [yp, pp] = gemm_outputs(y_opt, p, M, N, splits, silu_gu);
   TORCH_CHECK(N * K < (1LL << 40), "gemm too large");
   const c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
   RC(oamd::gemm_w4(ptr<bf16_t>(x), ptr<bf16_t>(w), yp, pp, (int)M, (int)N, (int)K, (int)splits, silu_gu, cur_stream()));
@@ -370,22 +352,8 @@ void gemm_skinny(const at::Tensor& x, const at::Tensor& w, const c10::optional<a
   TORCH_CHECK(N % (silu_gu ? 128 : 16) == 0, "gemm_skinny: N % 16 (128 for the fused SwiGLU)");
   TORCH_CHECK(splits >= 1 && splits <= 8 && K % (128 * splits) == 0, "gemm_skinny: K % (128 * splits)");
   TORCH_CHECK(!silu_gu || splits == 1, "fused SwiGLU needs splits = 1");
-  bf16_t* yp = nullptr;
-  if (y_opt.has_value()) {
-    CHECK_BF16(*y_opt); CHECK_CONTIG(*y_opt);
-    TORCH_CHECK(y_opt->dim() == 2 && y_opt->size(0) == M && y_opt->size(1) == (silu_gu ? N / 2 : N), "gemm shapes");
-    yp = ptr<bf16_t>(*y_opt);
-  } else {
-    TORCH_CHECK(splits > 1 && !silu_gu, "y may be omitted only for split-K slabs summed by the consumer");
-  }
-  float* pp = nullptr;
-  if (splits > 1) {
-    TORCH_CHECK(p.has_value(), "split-K needs a partial buffer");
-    CHECK_DT(*p, at::kFloat); CHECK_CONTIG(*p);
-    TORCH_CHECK(p->numel() >= splits * M * N, "partial buffer too small");
-    TORCH_CHECK((M * N) % 4 == 0 || yp == nullptr, "split-K reduce needs M * N % 4 == 0");
-    pp = p->data_ptr<float>();
-  }
+  const auto [yp, pp] = gemm_outputs(y_opt, p, M, N, splits, silu_gu);
+  TORCH_CHECK(splits == 1 || (M * N) % 4 == 0 || yp == nullptr, "split-K reduce needs M * N % 4 == 0");
   TORCH_CHECK(N * K < (1LL << 40) && M * K < (1LL << 31), "gemm too large");
   const c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
   RC(oamd::gemm_skinny(ptr<bf16_t>(x), ptr<bf16_t>(w), yp, pp, (int)M, (int)N, (int)K, (int)splits, silu_gu,

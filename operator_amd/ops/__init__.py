@@ -6,21 +6,25 @@ reference implementations in :mod:`operator_amd.ops.reference`.
 """
 from __future__ import annotations
 
-import json
 import os
 
 import torch
-import torch.nn.functional as F
 
 from . import reference
 from ._native import kernels, native_available, patterns
+# the bf16 GEMMs (plan, then launch) live in ops/gemm.py
+from .gemm import (BLAS_CALLS, BLAS_PLANNED, GEMM_DECODE_M, GU_BLOCK, LM_HEAD_MIN_N, PREFILL_BLAS, SKINNY_MAX_M,
+                   SplitK, gate_up_silu, gemm_plan, gemm_table, interleave_gate_up, linear, linear_tile, row_tile,
+                   skinny_plan, tile_ok, tile_out_ok)
 
 __all__ = [
     "rmsnorm", "silu_mul", "embedding", "rope_kv", "attn_prefill", "attn_decode", "attn_decode_rope", "sample",
     "sample_threshold",
     "kernels", "patterns", "native_available", "reference", "prefill_work_list", "prefill_block_q", "prefill_variant", "decode_splits",
-    "decode_workspace", "linear", "gemm_splits", "gemm_plan", "gate_up_silu", "interleave_gate_up",
+    "decode_workspace", "linear", "gemm_plan", "gemm_table", "gate_up_silu", "interleave_gate_up",
     "quantize_fp8", "silu_quantize_fp8", "linear_fp8", "fp8_plan", "SplitK", "linear_tile", "tile_ok", "BLAS_CALLS",
+    "skinny_plan", "row_tile", "tile_out_ok", "GU_BLOCK", "GEMM_DECODE_M", "SKINNY_MAX_M", "LM_HEAD_MIN_N",
+    "BLAS_PLANNED", "PREFILL_BLAS",
 ]
 
 # never split a sequence into pieces shorter than this / split only while B x Hkv
@@ -32,21 +36,6 @@ DECODE_TARGET_BLOCKS = int(os.environ.get("OAMD_DECODE_TARGET_BLOCKS", "256"))
 # attn_decode schedule bits (csrc/kernels/attn_decode.hip): 2 = NT 2 (two 16-token tiles per wave),
 # 4 = one kv-head across all sequences first (else a sequence's kv-heads back to back)
 DECODE_ATTN_VARIANT = int(os.environ.get("OAMD_DECODE_ATTN_VARIANT", "0"))
-
-
-class SplitK:
-    """A decode GEMM's output left as S fp32 split-K slabs [S, M, N]; the consumer
-    (rmsnorm) sums them, so the GEMM's separate reduction pass disappears."""
-
-    __slots__ = ("p", "S", "shape", "device", "dtype", "is_cuda")
-
-    def __init__(self, p: torch.Tensor, S: int, M: int, N: int):
-        self.p, self.S, self.shape = p, S, (M, N)
-        self.device, self.dtype, self.is_cuda = p.device, torch.bfloat16, True
-
-    def materialize(self) -> torch.Tensor:
-        M, N = self.shape
-        return self.p[: self.S * M * N].view(self.S, M, N).sum(0).to(torch.bfloat16)
 
 
 def rmsnorm(x, w: torch.Tensor, eps: float, residual: torch.Tensor | None = None,
@@ -83,79 +72,6 @@ def silu_mul(gu: torch.Tensor, out: torch.Tensor | None = None, block: int | Non
     o = out if out is not None else torch.empty(gu.shape[0], inter, dtype=gu.dtype, device=gu.device)
     kernels().silu_mul(gu, o, block or 0)
     return o
-
-
-GU_BLOCK = 64  # gate|up weight rows interleaved in 64-feature blocks (fused SwiGLU epilogue)
-
-
-def interleave_gate_up(g: torch.Tensor, u: torch.Tensor, block: int = GU_BLOCK) -> torch.Tensor:
-    """[g; u] rows -> blocks of ``block`` gate rows followed by the same features' up rows."""
-    inter, H = g.shape
-    return torch.stack([g.reshape(inter // block, block, H), u.reshape(inter // block, block, H)], 1).reshape(
-        2 * inter, H).contiguous()
-
-
-def gate_up_silu(x: torch.Tensor, wgu: torch.Tensor, block: int | None) -> torch.Tensor:
-    """silu(x Wg^T) * (x Wu^T) from the interleaved gate|up weight. Decode buckets run
-    one fused gfx950 kernel (GEMM + SwiGLU epilogue, no [M, 2I] intermediate);
-    other shapes run the GEMM then the silu_mul kernel."""
-    M, K = x.shape
-    N = wgu.shape[0]
-    if (x.is_cuda and block == 64 and x.dtype == torch.bfloat16 and M <= SKINNY_MAX_M and N % 128 == 0
-            and K % 128 == 0 and x.is_contiguous() and wgu.is_contiguous()
-            and skinny_plan(M, N, K) is not None and _gemm_table_get().get(("silu", M, N, K)) != "blas"):
-        y = torch.empty(M, N // 2, dtype=x.dtype, device=x.device)
-        kernels().gemm_skinny(x, wgu, y, None, 1, True)
-        return y
-    if (x.is_cuda and block == 64 and x.dtype == torch.bfloat16 and M % 64 == 0 and M <= 256 and N % 128 == 0
-            and K % 64 == 0 and x.is_contiguous() and wgu.is_contiguous()):
-        t = _gemm_table_get().get(("silu", M, N, K))
-        if t == "w4":   # four-wave 256-row kernel (gemm_w4.hip); the parent plan of the 256-row bucket is pp256
-            if M != 256:
-                raise ValueError(f"gemm table: plan 'w4' on silu,{M},{N},{K}: gemm_w4 takes the 256-row bucket only")
-            if DEC_GEMM_W4:
-                y = torch.empty(M, N // 2, dtype=x.dtype, device=x.device)
-                kernels().gemm_w4(x, wgu, y, None, 1, True)
-                return y
-            t = "pp256"
-        if isinstance(t, str) and t.startswith("pp"):   # ping-pong kernel, nt weight loads (bm 128 / 256)
-            y = torch.empty(M, N // 2, dtype=x.dtype, device=x.device)
-            bm = int(t[2:])
-            ws, fl = _pp_sk_workspace(x.device, N // 128) if (bm == 256 and PP_STREAM_K) else (None, None)
-            kernels().gemm_pp(x, wgu, y, None, 1, bm, True, True, False, ws, fl)
-            return y
-        if t != "blas":
-            bm = t[0] if t else row_tile(M)
-            ns = t[1] if t and len(t) > 1 else 3
-            y = torch.empty(M, N // 2, dtype=x.dtype, device=x.device)
-            kernels().gemm_decode(x, wgu, y, None, 1, 128, bm, True, False, ns)
-            return y
-    if block == 64 and tile_ok(x, wgu) and N % 128 == 0:
-        return linear_tile(x, wgu, silu_gu=True)   # prefill: SwiGLU fused into the tile epilogue
-    return silu_mul(linear(x, wgu), block=block)
-
-
-# Stream-K form of the 256-row gate|up+SwiGLU decode GEMM (csrc/kernels/gemm_pp.hip SK): one block per
-# CU over the flattened (tile, K-step) stream instead of one block per 128-feature tile (224 of 256 CUs
-# busy at the 8B shape). OAMD_PP_STREAM_K=1 turns it on (A/B runs).
-PP_STREAM_K = os.environ.get("OAMD_PP_STREAM_K", "0") == "1"
-# Table plans tagged "w4" run the four-wave 256-row decode GEMM (csrc/kernels/gemm_w4.hip, bitwise equal to
-# the parent plan's kernel); OAMD_DEC_GEMM_W4=0 runs the parent plan instead (A/B runs).
-DEC_GEMM_W4 = os.environ.get("OAMD_DEC_GEMM_W4", "1") != "0"
-_PP_SK_WS: dict = {}
-
-
-def _pp_sk_workspace(device, tiles: int):
-    """(fp32 partials, zeroed int flags) for the stream-K gate|up kernel, one pair per (device,
-    tile count), kept for the life of the process: captured decode graphs hold the pointers, and the
-    kernel leaves the flags zero. A stream runs one such GEMM at a time (the engine's decode stream)."""
-    key = (str(device), tiles)
-    ws = _PP_SK_WS.get(key)
-    if ws is None:
-        ws = (torch.empty(tiles * 32768, dtype=torch.float32, device=device),
-              torch.zeros(tiles, dtype=torch.int32, device=device))
-        _PP_SK_WS[key] = ws
-    return ws
 
 
 def embedding(ids: torch.Tensor, table: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -287,205 +203,6 @@ def attn_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, seq_lens: li
     else:
         kernels().attn_prefill(q, k, v, o, work[0], work[1], work[2], scale, var)
     return o
-
-
-GEMM_DECODE_M = (64, 128, 256)  # decode buckets the gfx950 gemm_decode kernel is tuned for
-_GEMM_TABLE_PATH = os.environ.get("OAMD_GEMM_TABLE") or os.path.join(os.path.dirname(os.path.abspath(__file__)),
-                                                                     "gemm_tuned.json")
-_gemm_table: dict | None = None
-
-
-def _gemm_table_get() -> dict:
-    """Measured best (bm, bn, splits) per decode GEMM shape on MI355X, written by
-    ``tools/bench_gemm.py --write-table`` ("blas" = hipBLASLt wins that shape)."""
-    global _gemm_table
-    if _gemm_table is None:
-        try:
-            with open(_GEMM_TABLE_PATH) as f:
-                _gemm_table = {tuple(x if x in ("silu", "skinny") else int(x) for x in k.split(",")): v
-                               for k, v in json.load(f).items()}
-        except (OSError, ValueError):
-            _gemm_table = {}
-    return _gemm_table
-
-
-def row_tile(M: int) -> int:
-    """Largest gemm_decode row tile (256, 128, 64) dividing M (M % 64 == 0): a bucket of
-    192 rows runs three 64-row tiles, not one 192-row tile the kernel has no variant for."""
-    return next(b for b in (256, 128, 64) if M % b == 0)
-
-
-LM_HEAD_MIN_N = 32768
-
-
-def _measured_blas(M: int, N: int, K: int) -> bool:
-    """The tuned table measured hipBLASLt fastest for this decode-bucket shape (small-M
-    GEMMs that neither the decode kernels nor the 256-row tile kernel win)."""
-    if N >= LM_HEAD_MIN_N:   # vocab projections always run on gemm_tile (weight-streaming bound there)
-        return False
-    t = _gemm_table_get()
-    return t.get(("skinny", M, N, K) if M <= SKINNY_MAX_M else (M, N, K)) == "blas"
-
-
-def gemm_splits(M: int, N: int, K: int) -> int:
-    """Heuristic split-K ways for gemm_decode (shapes not in the tuned table): the
-    smallest S | 8 whose (N/64) x S blocks reach one block per CU (256)."""
-    tiles = N // 64
-    best = 1
-    for S in (1, 2, 4, 8):
-        if K % (64 * S):
-            break
-        best = S
-        if tiles * S >= 256:
-            return S
-    return best
-
-
-def gemm_plan(M: int, N: int, K: int):
-    """(bm, bn, splits) for the gfx950 gemm_decode kernel, or None for hipBLASLt."""
-    if M % 64 or N % 64 or K % 64 or M > 256:
-        return None
-    t = _gemm_table_get().get((M, N, K))
-    if t in ("blas", "tile"):   # hipBLASLt / the 256x256-tile kernel (linear decides which)
-        return None
-    if t is not None:
-        return tuple(t)   # (bm, bn, S[, stages]) for gemm_decode
-    return (row_tile(M), 64, gemm_splits(M, N, K))
-
-
-SKINNY_MAX_M = 32
-
-
-def skinny_plan(M: int, N: int, K: int) -> int | None:
-    """Split-K count for the gfx950 gemm_skinny kernel (M <= 32 decode buckets), or None
-    for hipBLASLt: tuned table entry ``skinny,M,N,K`` if present, else split K until
-    the 16-row tiles give >= 512 blocks (K permitting)."""
-    if M > SKINNY_MAX_M or N % 16 or K % 128 or os.environ.get("OAMD_SKINNY", "1") == "0":
-        return None
-    t = _gemm_table_get().get(("skinny", M, N, K))
-    if t == "blas":
-        return None
-    if t is not None:
-        return int(t)
-    S = 1
-    while (N // 16) * S < 512 and S < 8 and K % (128 * S * 2) == 0:
-        S *= 2
-    return S
-
-
-# Every GPU GEMM of the model runs on the hand-written gfx950 kernels: prefill projections (M > 256
-# rows) on gemm_tile's persistent p5 schedule (csrc/kernels/gemm_tile.hip), decode buckets on
-# gemm_pp / gemm_tn / gemm_w4 / gemm_skinny, the lm_head on gemm_tile, fp8 on gemm_fp8. hipBLASLt is reached
-# only by shapes none of them takes (K % 64 != 0, N % 16 != 0, non-bf16), counted in BLAS_CALLS.
-# OAMD_PREFILL_BLAS=1 routes the plain prefill projections (QKV, O, down) to hipBLASLt instead, for
-# A/B runs against the vendor library (profiles/gemm_tile_p5_vs_hipblaslt_r6.jsonl).
-PREFILL_BLAS = os.environ.get("OAMD_PREFILL_BLAS", "0") == "1"
-BLAS_CALLS = {"n": 0}   # GPU GEMMs that FELL BACK to hipBLASLt (tests assert it stays 0 on model shapes)
-BLAS_PLANNED = {"n": 0}   # plain prefill projections run on hipBLASLt by design (PREFILL_BLAS)
-
-
-def _blas(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor | None, bias: torch.Tensor | None,
-          planned: bool = False):
-    if x.is_cuda and planned:
-        BLAS_PLANNED["n"] += 1
-    elif x.is_cuda:
-        BLAS_CALLS["n"] += 1
-        if os.environ.get("OAMD_FORBID_BLAS") == "1":
-            raise RuntimeError(f"hipBLASLt fallback for x {tuple(x.shape)} {x.dtype}, w {tuple(w.shape)} "
-                               "(OAMD_FORBID_BLAS=1)")
-    if out is not None:
-        return F.linear(x, w, bias, out=out) if bias is None else out.copy_(F.linear(x, w, bias))
-    return F.linear(x, w, bias)
-
-
-def tile_ok(x: torch.Tensor, w: torch.Tensor) -> bool:
-    """Shapes the 256x256-tile gfx950 GEMM (gemm_tile) takes: bf16, K % 64, N % 16."""
-    return (x.is_cuda and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and x.dim() == 2
-            and x.is_contiguous() and w.is_contiguous() and x.shape[1] % 64 == 0 and w.shape[0] % 16 == 0
-            and x.shape[0] >= 1)
-
-
-def tile_out_ok(out: torch.Tensor | None) -> bool:
-    """An explicit output gemm_tile can write: unit column stride, a row stride that is a
-    multiple of 4 elements and an 8-byte-aligned base (its epilogue stores 4 bf16 at once);
-    anything else falls back instead of tripping the binding's TORCH_CHECK."""
-    return out is None or (out.dim() == 2 and out.stride(1) == 1 and out.stride(0) % 4 == 0
-                           and out.data_ptr() % 8 == 0 and out.dtype == torch.bfloat16)
-
-
-def linear_tile(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor | None = None,
-                bias: torch.Tensor | None = None, silu_gu: bool = False) -> torch.Tensor:
-    """Prefill / lm_head GEMM on the compute-bound gfx950 tile kernel (256 x 256 tiles,
-    LDS-DMA ping-pong pipeline; fused bias or SwiGLU epilogue)."""
-    M = x.shape[0]
-    N = w.shape[0]
-    y = out if out is not None else torch.empty(M, N // 2 if silu_gu else N, dtype=x.dtype, device=x.device)
-    kernels().gemm_tile(x, w, y, bias, silu_gu)
-    return y
-
-
-def linear(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor | None = None, splits: int | None = None,
-           partial: torch.Tensor | None = None, bn: int | None = None, bm: int | None = None,
-           defer_reduce: bool = False, stages: int | None = None, bias: torch.Tensor | None = None):
-    """y = x @ w^T (+ bias) in bf16 on the gfx950 kernels: M <= 32 decode buckets on the
-    weight-streaming gemm_skinny, M in {64, 128, 256} on the LDS-staged split-K
-    gemm_decode (tuned tables), everything else (prefill, the lm_head, biased
-    projections) on the 256x256-tile gemm_tile (persistent p5 past 256 rows). hipBLASLt only
-    for shapes none of them takes (K % 64 != 0, N % 16 != 0, non-bf16), for decode shapes the
-    tuned table measured it fastest on, or under OAMD_PREFILL_BLAS=1 (A/B); CPU tensors on torch."""
-    M, K = x.shape
-    N = w.shape[0]
-    plan = None
-    if bias is not None:
-        if tile_ok(x, w) and tile_out_ok(out):
-            return linear_tile(x, w, out, bias)
-        return _blas(x, w, out, bias)
-    if x.is_cuda and bm is None and bn is None and splits is None and _measured_blas(M, N, K):
-        return _blas(x, w, out, None)
-    if PREFILL_BLAS and x.is_cuda and M > 256 and N < LM_HEAD_MIN_N and splits is None and x.dtype == torch.bfloat16:
-        return _blas(x, w, out, None, planned=True)
-    if (x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() and w.is_contiguous() and M <= SKINNY_MAX_M
-            and bm is None and bn is None):
-        S = splits or skinny_plan(M, N, K)
-        if S is not None:
-            if S > 1 and (partial is None or partial.numel() < S * M * N):
-                partial = torch.empty(S * M * N, dtype=torch.float32, device=x.device)
-            if defer_reduce and S > 1 and out is None:
-                kernels().gemm_skinny(x, w, None, partial, S, False)
-                return SplitK(partial, S, M, N)
-            y = out if out is not None else torch.empty(M, N, dtype=x.dtype, device=x.device)
-            kernels().gemm_skinny(x, w, y, partial if S > 1 else None, S, False)
-            return y
-    if x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() and w.is_contiguous():
-        plan = gemm_plan(M, N, K)
-        if plan is None and (splits or bn or bm) and M % 64 == 0 and M <= 256 and N % 64 == 0 and K % 64 == 0:
-            plan = (row_tile(M), 64, 1)  # explicit request (tests / tuning)
-    if plan is None:
-        if tile_ok(x, w) and tile_out_ok(out):
-            return linear_tile(x, w, out)
-        return _blas(x, w, out, None)
-    # a fifth element "w4": the table plan runs on gemm_w4 (the first four stay its parent gemm_decode plan)
-    if len(plan) > 4 and plan[4] == "w4" and (M != 256 or tuple(plan[:2]) != (256, 128)):
-        raise ValueError(f"gemm table: plan {plan} on {M},{N},{K}: gemm_w4 runs M = 256 as 256 x 128 tiles only")
-    w4 = (DEC_GEMM_W4 and len(plan) > 4 and plan[4] == "w4" and bm is None and bn is None
-          and splits is None and stages is None)
-    bm, bn, S = bm or plan[0], bn or plan[1], splits or plan[2]
-    ns = stages or (plan[3] if len(plan) > 3 else 3)
-    if S > 1 and (partial is None or partial.numel() < S * M * N):
-        partial = torch.empty(S * M * N, dtype=torch.float32, device=x.device)
-    if w4:
-        if defer_reduce and S > 1 and out is None:
-            kernels().gemm_w4(x, w, None, partial, S, False)
-            return SplitK(partial, S, M, N)
-        y = out if out is not None else torch.empty(M, N, dtype=x.dtype, device=x.device)
-        kernels().gemm_w4(x, w, y, partial if S > 1 else None, S, False)
-        return y
-    if defer_reduce and S > 1 and out is None:
-        kernels().gemm_decode(x, w, None, partial, S, bn, bm, False, False, ns)
-        return SplitK(partial, S, M, N)
-    y = out if out is not None else torch.empty(M, N, dtype=x.dtype, device=x.device)
-    kernels().gemm_decode(x, w, y, partial if S > 1 else None, S, bn, bm, False, False, ns)
-    return y
 
 
 FP8_MAX = 448.0  # OCP e4m3fn

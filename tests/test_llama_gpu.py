@@ -333,7 +333,7 @@ def test_llama3_8b_shapes_never_fall_back_to_hipblaslt(monkeypatch, prefill_blas
     """Every GEMM of the Llama-3-8B shapes runs where it is planned to: with
     OAMD_FORBID_BLAS=1 any hipBLASLt FALLBACK raises. Two layers of the real architecture,
     prefill batches of 1k and 4k packed tokens (tails included) and the M = 64 / 256
-    decode buckets. With ops.PREFILL_BLAS the plain prefill projections (QKV, O, down:
+    decode buckets. With ops.gemm.PREFILL_BLAS the plain prefill projections (QKV, O, down:
     3 per layer and batch) are planned hipBLASLt calls and nothing else is; without it
     every GEMM runs on the gfx950 kernels."""
     from dataclasses import replace
@@ -341,7 +341,7 @@ def test_llama3_8b_shapes_never_fall_back_to_hipblaslt(monkeypatch, prefill_blas
     from operator_amd import ops
 
     monkeypatch.setenv("OAMD_FORBID_BLAS", "1")
-    monkeypatch.setattr(ops, "PREFILL_BLAS", prefill_blas)
+    monkeypatch.setattr(ops.gemm, "PREFILL_BLAS", prefill_blas)
     cfg = replace(get_config("llama3-8b"), layers=2)
     m = LlamaModel(cfg, device="cuda").init_random(seed=3)
     kv = PagedKVCache(cfg.layers, 128, cfg.kv_heads, 128, 64, device="cuda")

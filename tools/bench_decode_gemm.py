@@ -83,29 +83,34 @@ def main() -> int:
             cands["table+norm"] = lambda: norm(ops.linear(x, nxt(), defer_reduce=True))
         if a.w4 and M == 256:
             # parent plan against the four-wave kernel (gemm_w4.hip), both through ops.linear /
-            # ops.gate_up_silu: "parent" = the table plan with OAMD_DEC_GEMM_W4=0, "w4" = the plan
-            # tagged w4 with the slice count of --w4-splits
-            tab = ops._gemm_table_get()
+            # ops.gate_up_silu, each arm installing its plan in the table: "parent" = pp256 for the
+            # SwiGLU shape, else the table plan without a w4 tag; "w4" = the plan tagged w4 with the
+            # slice count of --w4-splits
+            tab = ops.gemm_table()
             key = ("silu", M, N, K) if silu else (M, N, K)
             base = tab.get(key)
             S4 = {k: int(v) for k, v in (kv.split("=") for kv in a.w4_splits.split(","))}.get(name, 1)
             if silu:
-                w4_plan = "w4"
+                parent_plan, w4_plan = "pp256", "w4"
             else:
-                b = list(base[:4]) if isinstance(base, (list, tuple)) else [256, 128, S4, 3]
-                w4_plan = [256, 128, S4, b[3] if len(b) > 3 else 3, "w4"]
+                b = list(base[:4]) if isinstance(base, (list, tuple)) else None
+                parent_plan = b if b is not None else base   # no entry (None): the default plan
+                w4_plan = [256, 128, S4, b[3] if b and len(b) > 3 else 3, "w4"]
 
-            def arm(plan, flag, fn):
+            def arm(plan, fn):
                 def run():
-                    tab[key], ops.DEC_GEMM_W4 = plan, flag
+                    if plan is None:
+                        tab.pop(key, None)
+                    else:
+                        tab[key] = plan
                     return fn()
                 return run
 
             table_arms = dict(cands)
             cands = {}
             for k, fn in table_arms.items():
-                cands[k.replace("table", "parent")] = arm(base, False, fn)
-                cands[k.replace("table", "w4")] = arm(w4_plan, True, fn)
+                cands[k.replace("table", "parent")] = arm(parent_plan, fn)
+                cands[k.replace("table", "w4")] = arm(w4_plan, fn)
         if a.tile:
             C = ops.kernels()
             P = torch.empty(16 * M * N, dtype=torch.float32, device="cuda")

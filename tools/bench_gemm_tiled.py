@@ -38,7 +38,7 @@ for name, (N, K) in shapes.items():
     for M in (64, 128, 256):
         x = torch.randn(M, K, device="cuda", dtype=torch.bfloat16)
         plan = ops.gemm_plan(M, N, K) or (min(M, 256), 128 if N >= 192 * 128 else 64, 1)
-        bm, bn, S = plan
+        bm, bn, S = plan[:3]
         y = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
         part = torch.empty(max(1, S) * M * N, device="cuda", dtype=torch.float32)
         C = ops.kernels()
