@@ -9,6 +9,7 @@
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 
+#include "bind_check.h"
 #include "kernels/kernels.h"
 #include "kernels/scan.h"
 
@@ -18,10 +19,6 @@ using oamd::bf16_t;
 
 hipStream_t cur_stream() { return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream(); }
 
-#define CHECK_DEV(t) TORCH_CHECK((t).is_cuda(), #t " must be a GPU tensor")
-#define CHECK_CONTIG(t) TORCH_CHECK((t).is_contiguous(), #t " must be contiguous")
-#define CHECK_DT(t, dt) TORCH_CHECK((t).scalar_type() == (dt), #t " has wrong dtype ", (t).scalar_type())
-#define CHECK_BF16(t) CHECK_DT(t, at::kBFloat16)
 #define ROWMAJOR_VEC(t) \
   TORCH_CHECK((t).dim() == 2 && (t).stride(1) == 1 && (t).stride(0) % 8 == 0, #t " must be [rows, cols] row-major with 16-B aligned rows")
 #define RC(call)                                                           \
@@ -35,19 +32,21 @@ T* ptr(const at::Tensor& t) { return reinterpret_cast<T*>(t.data_ptr()); }
 template <typename T>
 T* optr(const c10::optional<at::Tensor>& t) { return t.has_value() ? reinterpret_cast<T*>(t->data_ptr()) : nullptr; }
 
-void rmsnorm(const at::Tensor& x, const c10::optional<at::Tensor>& residual, const at::Tensor& w,
-             at::Tensor& y, double eps, const c10::optional<at::Tensor>& partial, int64_t splits, bool tiled_out) {
-  CHECK_DEV(x); CHECK_BF16(x); CHECK_BF16(w); CHECK_BF16(y); ROWMAJOR_VEC(x); ROWMAJOR_VEC(y);
-  CHECK_CONTIG(w);
-  const int64_t rows = x.size(0), hidden = x.size(1);
-  const float* xp = nullptr;
-  if (partial.has_value()) {  // x = bf16(sum of `splits` fp32 [rows, hidden] slabs); x only gives the shape
-    CHECK_DT(*partial, at::kFloat); CHECK_CONTIG(*partial);
-    TORCH_CHECK(splits >= 1 && partial->numel() >= splits * rows * hidden, "rmsnorm: partial slabs too small");
-    xp = partial->data_ptr<float>();
-  }
+// x: bf16 [rows, hidden], or None with `slabs` = the `splits` fp32 split-K slabs of those rows; the
+// shape is y's.
+void rmsnorm(const c10::optional<at::Tensor>& x, const c10::optional<at::Tensor>& residual, const at::Tensor& w,
+             at::Tensor& y, double eps, const c10::optional<at::Tensor>& slabs, int64_t splits, bool tiled_out) {
+  CHECK_DEV(y); CHECK_BF16(w); CHECK_BF16(y); ROWMAJOR_VEC(y); CHECK_CONTIG(w);
+  const int64_t rows = y.size(0), hidden = y.size(1);
   TORCH_CHECK(hidden % 8 == 0 && hidden <= 256 * 8 * 8, "hidden must be a multiple of 8 and <= 16384");
-  TORCH_CHECK(w.numel() == hidden && y.size(0) == rows && y.size(1) == hidden, "rmsnorm shape mismatch");
+  TORCH_CHECK(w.numel() == hidden, "rmsnorm shape mismatch");
+  oamd::Slabs sl;
+  if (slabs_given(x, slabs, "rmsnorm")) {
+    sl = slab_input(*slabs, splits, rows, hidden, "rmsnorm");
+  } else {
+    CHECK_DEV(*x); CHECK_BF16(*x); ROWMAJOR_VEC(*x);
+    TORCH_CHECK(x->size(0) == rows && x->size(1) == hidden, "rmsnorm shape mismatch");
+  }
   int64_t rstride = 0;
   if (residual.has_value()) {
     CHECK_BF16(*residual); ROWMAJOR_VEC(*residual);
@@ -57,10 +56,10 @@ void rmsnorm(const at::Tensor& x, const c10::optional<at::Tensor>& residual, con
   // tiled_out: y (contiguous, [rows, hidden] elements) receives the gemm_xr activation layout
   TORCH_CHECK(!tiled_out || (rows % 16 == 0 && hidden % 64 == 0 && y.is_contiguous()),
               "rmsnorm: tiled output needs rows % 16 == 0, hidden % 64 == 0 and a contiguous y");
-  const c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
-  RC(oamd::rmsnorm(ptr<bf16_t>(x), optr<bf16_t>(residual), ptr<bf16_t>(w), ptr<bf16_t>(y), (int)rows,
-                   (int)hidden, x.stride(0), rstride, tiled_out ? -1 : y.stride(0), (float)eps, xp, (int)splits,
-                   cur_stream()));
+  const c10::hip::HIPGuardMasqueradingAsCUDA g(y.device());
+  RC(oamd::rmsnorm(optr<bf16_t>(x), optr<bf16_t>(residual), ptr<bf16_t>(w), ptr<bf16_t>(y), (int)rows,
+                   (int)hidden, x.has_value() ? x->stride(0) : 0, rstride, tiled_out ? -1 : y.stride(0), (float)eps,
+                   sl, cur_stream()));
 }
 
 // gemm_xr (csrc/kernels/gemm_xr.hip): the 256-row decode GEMM with register-streamed activations.
@@ -156,29 +155,27 @@ static bool kv_is_fp8(const at::Tensor& t) {
   return t.scalar_type() == at::kFloat8_e4m3fn || t.scalar_type() == at::kByte;
 }
 
-void rope_kv(const at::Tensor& qkv, const at::Tensor& pos, const at::Tensor& cos_t, const at::Tensor& sin_t,
-             int64_t Hq, int64_t Hkv, at::Tensor& q_out, const c10::optional<at::Tensor>& k_out,
-             const c10::optional<at::Tensor>& v_out, const c10::optional<at::Tensor>& k_cache,
-             const c10::optional<at::Tensor>& v_cache, const c10::optional<at::Tensor>& slots,
-             const c10::optional<at::Tensor>& partial, int64_t splits, const c10::optional<at::Tensor>& bias,
-             double k_scale, double v_scale) {
+// qkv: bf16 [T, (Hq+2Hkv)D], or None with `slabs` = the `splits` fp32 split-K slabs of those rows
+// (T = pos.numel()).
+void rope_kv(const c10::optional<at::Tensor>& qkv, const at::Tensor& pos, const at::Tensor& cos_t,
+             const at::Tensor& sin_t, int64_t Hq, int64_t Hkv, at::Tensor& q_out,
+             const c10::optional<at::Tensor>& k_out, const c10::optional<at::Tensor>& v_out,
+             const c10::optional<at::Tensor>& k_cache, const c10::optional<at::Tensor>& v_cache,
+             const c10::optional<at::Tensor>& slots, const c10::optional<at::Tensor>& slabs, int64_t splits,
+             const c10::optional<at::Tensor>& bias, double k_scale, double v_scale) {
   CHECK_DT(pos, at::kLong); CHECK_CONTIG(pos); CHECK_DEV(pos);
   CHECK_DT(cos_t, at::kFloat); CHECK_DT(sin_t, at::kFloat); CHECK_CONTIG(cos_t); CHECK_CONTIG(sin_t);
   const int64_t T = pos.numel();
   const int64_t D = cos_t.size(1) * 2;
   TORCH_CHECK(D == 128, "only head_dim 128 is supported");
-  const float* xp = nullptr;
-  const bf16_t* qp = nullptr;
+  oamd::Slabs sl;
   int64_t qstride = 0;
-  if (partial.has_value()) {  // qkv = bf16(sum of `splits` fp32 [T, (Hq+2Hkv)D] slabs); qkv unused
-    CHECK_DT(*partial, at::kFloat); CHECK_CONTIG(*partial);
-    TORCH_CHECK(splits >= 1 && partial->numel() >= splits * T * (Hq + 2 * Hkv) * D, "rope_kv: slabs too small");
-    xp = partial->data_ptr<float>();
+  if (slabs_given(qkv, slabs, "rope_kv")) {
+    sl = slab_input(*slabs, splits, T, (Hq + 2 * Hkv) * D, "rope_kv");
   } else {
-    CHECK_DEV(qkv); CHECK_BF16(qkv); ROWMAJOR_VEC(qkv);
-    TORCH_CHECK(qkv.size(0) == T && qkv.size(1) == (Hq + 2 * Hkv) * D, "qkv must be [T, (Hq+2Hkv)*D]");
-    qp = ptr<bf16_t>(qkv);
-    qstride = qkv.stride(0);
+    CHECK_DEV(*qkv); CHECK_BF16(*qkv); ROWMAJOR_VEC(*qkv);
+    TORCH_CHECK(qkv->size(0) == T && qkv->size(1) == (Hq + 2 * Hkv) * D, "qkv must be [T, (Hq+2Hkv)*D]");
+    qstride = qkv->stride(0);
   }
   TORCH_CHECK(pos.numel() == T && sin_t.sizes() == cos_t.sizes(), "pos/cos/sin shape");
   CHECK_BF16(q_out); CHECK_CONTIG(q_out);
@@ -206,14 +203,14 @@ void rope_kv(const at::Tensor& qkv, const at::Tensor& pos, const at::Tensor& cos
   const c10::hip::HIPGuardMasqueradingAsCUDA g(pos.device());
   const bool fp8 = k_cache.has_value() && kv_is_fp8(*k_cache);
   TORCH_CHECK(k_scale > 0 && v_scale > 0, "KV scales must be positive");
-  RC(oamd::rope_kv(qp, qstride, ptr<int64_t>(pos), ptr<float>(cos_t), ptr<float>(sin_t),
+  RC(oamd::rope_kv(optr<bf16_t>(qkv), qstride, ptr<int64_t>(pos), ptr<float>(cos_t), ptr<float>(sin_t),
                    (int)T, (int)Hq, (int)Hkv, (int)D, ptr<bf16_t>(q_out), optr<bf16_t>(k_out), optr<bf16_t>(v_out),
                    k_cache.has_value() ? k_cache->data_ptr() : nullptr,
                    v_cache.has_value() ? v_cache->data_ptr() : nullptr, optr<int64_t>(slots), page, cos_t.size(0),
-                   xp, (int)splits, optr<bf16_t>(bias), fp8, (float)k_scale, (float)v_scale, cur_stream()));
+                   sl, optr<bf16_t>(bias), fp8, (float)k_scale, (float)v_scale, cur_stream()));
 }
 
-// y / p of the split-K decode GEMMs (gemm_decode, gemm_pp, gemm_w4, gemm_skinny) as raw pointers: y [M, N]
+// y / p of the split-K decode GEMMs (gemm_decode, gemm_pp, gemm_w4, gemm_skinny, gemm_fp8) as raw pointers: y [M, N]
 // (N / 2 with the SwiGLU epilogue) may be omitted only where the consumer sums the fp32 slabs (splits > 1, no
 // SwiGLU); splits > 1 needs a contiguous fp32 p of at least splits * M * N.
 std::pair<bf16_t*, float*> gemm_outputs(const c10::optional<at::Tensor>& y_opt, const c10::optional<at::Tensor>& p_opt,
@@ -230,10 +227,7 @@ std::pair<bf16_t*, float*> gemm_outputs(const c10::optional<at::Tensor>& y_opt, 
   float* pp = nullptr;
   if (splits > 1) {
     TORCH_CHECK(p_opt.has_value(), "split-K needs a partial buffer");
-    const at::Tensor& p = *p_opt;
-    CHECK_DEV(p); CHECK_DT(p, at::kFloat); CHECK_CONTIG(p);
-    TORCH_CHECK(p.numel() >= splits * M * N, "partial buffer too small");
-    pp = p.data_ptr<float>();
+    pp = const_cast<float*>(slab_input(*p_opt, splits, M, N, "gemm").p);
   }
   return {yp, pp};
 }
@@ -374,55 +368,50 @@ void quantize_fp8(const at::Tensor& x, at::Tensor& q, at::Tensor& sx) {
                              x.stride(0), cur_stream()));
 }
 
-// gu: bf16 [M, 2I] gate|up rows, or (slabs given) a shape carrier [M, 2I] whose values are the
-// S fp32 split-K slabs [S, M, 2I] of the producing GEMM.
-void silu_quantize_fp8(const at::Tensor& gu, at::Tensor& q, at::Tensor& sx, const c10::optional<at::Tensor>& slabs,
-                       int64_t splits) {
-  CHECK_DEV(gu); CHECK_CONTIG(q); CHECK_CONTIG(sx); CHECK_DT(sx, at::kFloat);
-  TORCH_CHECK(gu.dim() == 2 && gu.stride(1) == 1, "gu must be [M, 2I] row-major");
+// gu: bf16 [M, 2I] gate|up rows, or None with `slabs` = the `splits` fp32 split-K slabs [S, M, 2I] of
+// the producing GEMM; q [M, I] gives the shape.
+void silu_quantize_fp8(const c10::optional<at::Tensor>& gu, at::Tensor& q, at::Tensor& sx,
+                       const c10::optional<at::Tensor>& slabs, int64_t splits) {
+  CHECK_DEV(q); CHECK_DEV(sx); CHECK_CONTIG(q); CHECK_CONTIG(sx); CHECK_DT(sx, at::kFloat);
   TORCH_CHECK(q.scalar_type() == at::kByte || q.scalar_type() == at::kFloat8_e4m3fn, "q must be uint8 / e4m3fn");
-  const int64_t M = gu.size(0), I = gu.size(1) / 2;
-  TORCH_CHECK(gu.size(1) % 128 == 0 && I <= 16384, "silu_quantize_fp8: 2I % 128 == 0, I <= 16384");
-  TORCH_CHECK(q.numel() == M * I && sx.numel() == M, "silu_quantize_fp8 shapes");
-  const float* pp = nullptr;
-  if (slabs.has_value()) {
-    CHECK_DT(*slabs, at::kFloat); CHECK_CONTIG(*slabs);
-    TORCH_CHECK(splits >= 1 && slabs->numel() >= splits * M * 2 * I, "slabs: fp32 [splits, M, 2I]");
-    pp = slabs->data_ptr<float>();
+  TORCH_CHECK(q.dim() == 2, "q must be [M, I]");
+  const int64_t M = q.size(0), I = q.size(1);
+  TORCH_CHECK(I % 64 == 0 && I <= 16384, "silu_quantize_fp8: 2I % 128 == 0, I <= 16384");
+  TORCH_CHECK(sx.numel() == M, "silu_quantize_fp8 shapes");
+  oamd::Slabs sl;
+  int64_t ld = 2 * I;
+  if (slabs_given(gu, slabs, "silu_quantize_fp8")) {
+    sl = slab_input(*slabs, splits, M, 2 * I, "silu_quantize_fp8");
   } else {
-    CHECK_BF16(gu);
-    TORCH_CHECK(gu.stride(0) % 8 == 0 && reinterpret_cast<uintptr_t>(gu.data_ptr()) % 16 == 0,
+    CHECK_DEV(*gu); CHECK_BF16(*gu);
+    TORCH_CHECK(gu->dim() == 2 && gu->stride(1) == 1, "gu must be [M, 2I] row-major");
+    TORCH_CHECK(gu->size(0) == M && gu->size(1) == 2 * I, "silu_quantize_fp8 shapes");
+    TORCH_CHECK(gu->stride(0) % 8 == 0 && reinterpret_cast<uintptr_t>(gu->data_ptr()) % 16 == 0,
                 "silu_quantize_fp8: gu needs a 16-B aligned base and a row stride that is a multiple of 8 elements");
+    ld = gu->stride(0);
   }
-  const c10::hip::HIPGuardMasqueradingAsCUDA g(gu.device());
-  RC(oamd::silu_quantize_fp8(pp != nullptr ? nullptr : ptr<bf16_t>(gu), pp, (int)splits,
-                             static_cast<uint8_t*>(q.data_ptr()), ptr<float>(sx), (int)M, (int)I,
-                             pp != nullptr ? 2 * I : gu.stride(0), cur_stream()));
+  const c10::hip::HIPGuardMasqueradingAsCUDA g(q.device());
+  RC(oamd::silu_quantize_fp8(optr<bf16_t>(gu), sl, static_cast<uint8_t*>(q.data_ptr()), ptr<float>(sx), (int)M,
+                             (int)I, ld, cur_stream()));
 }
 
 void gemm_fp8(const at::Tensor& x8, const at::Tensor& w8, const at::Tensor& sx, const at::Tensor& sw, at::Tensor& y,
               const c10::optional<at::Tensor>& p, int64_t splits, int64_t bn, int64_t bm, bool reduce) {
-  CHECK_DEV(x8); CHECK_CONTIG(x8); CHECK_CONTIG(w8); CHECK_CONTIG(sx); CHECK_CONTIG(sw); CHECK_BF16(y);
-  CHECK_CONTIG(y); CHECK_DT(sx, at::kFloat); CHECK_DT(sw, at::kFloat);
+  CHECK_DEV(x8); CHECK_CONTIG(x8); CHECK_CONTIG(w8); CHECK_CONTIG(sx); CHECK_CONTIG(sw);
+  CHECK_DT(sx, at::kFloat); CHECK_DT(sw, at::kFloat);
   for (auto* t : {&x8, &w8})
     TORCH_CHECK(t->scalar_type() == at::kByte || t->scalar_type() == at::kFloat8_e4m3fn, "fp8 operands");
   TORCH_CHECK(x8.dim() == 2 && w8.dim() == 2, "x8 [M,K], w8 [N,K]");
   const int64_t M = x8.size(0), K = x8.size(1), N = w8.size(0);
-  TORCH_CHECK(w8.size(1) == K && y.size(0) == M && y.size(1) == N && sx.numel() == M && sw.numel() == N,
-              "gemm_fp8 shapes");
+  TORCH_CHECK(w8.size(1) == K && sx.numel() == M && sw.numel() == N, "gemm_fp8 shapes");
   TORCH_CHECK((bn == 64 || bn == 128) && N % bn == 0, "gemm_fp8: N % bn");
   TORCH_CHECK(bm == 64 || bm == 128 || bm == 256, "gemm_fp8: bm in {64,128,256}");
   TORCH_CHECK(splits >= 1 && splits <= 16 && K % 128 == 0 && K / 128 >= splits, "gemm_fp8: K % 128, 1 <= splits <= min(16, K / 128)");
-  float* pp = nullptr;
-  if (splits > 1) {
-    TORCH_CHECK(p.has_value() && p->scalar_type() == at::kFloat && p->numel() >= splits * M * N,
-                "split-K needs an fp32 partial buffer");
-    pp = p->data_ptr<float>();
-  }
+  const auto [yp, pp] = gemm_outputs(y, p, M, N, splits, false);
   const c10::hip::HIPGuardMasqueradingAsCUDA g(x8.device());
   RC(oamd::gemm_fp8(static_cast<const uint8_t*>(x8.data_ptr()), static_cast<const uint8_t*>(w8.data_ptr()),
-                    ptr<float>(sx), ptr<float>(sw), (reduce || splits == 1) ? ptr<bf16_t>(y) : nullptr, pp, (int)M, (int)N, (int)K, (int)splits, (int)bn,
-                    (int)bm, cur_stream()));
+                    ptr<float>(sx), ptr<float>(sw), (reduce || splits == 1) ? yp : nullptr, pp, (int)M, (int)N, (int)K,
+                    (int)splits, (int)bn, (int)bm, cur_stream()));
 }
 
 void score_events(const at::Tensor& keys, const at::Tensor& hit_doc, const at::Tensor& doc_ptr,
@@ -456,15 +445,23 @@ void score_events(const at::Tensor& keys, const at::Tensor& hit_doc, const at::T
                         ptr<int>(ev_pat), ptr<int>(ev_line), ptr<int>(order), ptr<int>(summary), cur_stream()));
 }
 
-void attn_decode(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
+// Exactly one of q (bf16 [B, Hq, D], rotated by rope_kv) and the QKV projection of the decode step,
+// whose RoPE + KV write are then folded in: rope_x (bf16 rows [B, (Hq+2Hkv)D]) or rope_slabs (its
+// `rope_splits` fp32 split-K slabs). Without q, out [B, Hq, D] gives the shape.
+void attn_decode(const c10::optional<at::Tensor>& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
                  const at::Tensor& block_tables, const at::Tensor& seq_lens, at::Tensor& out,
                  at::Tensor& o_part, at::Tensor& ml_part, int64_t num_splits, double scale, int64_t variant,
                  double k_scale, double v_scale, const c10::optional<at::Tensor>& q8,
-                 const c10::optional<at::Tensor>& sx, const c10::optional<at::Tensor>& rope_x, int64_t rope_splits,
+                 const c10::optional<at::Tensor>& sx, const c10::optional<at::Tensor>& rope_x,
+                 const c10::optional<at::Tensor>& rope_slabs, int64_t rope_splits,
                  const c10::optional<at::Tensor>& pos, const c10::optional<at::Tensor>& cos_t,
                  const c10::optional<at::Tensor>& sin_t, const c10::optional<at::Tensor>& slots,
                  const c10::optional<at::Tensor>& bias) {
-  CHECK_DEV(q); CHECK_BF16(q); CHECK_CONTIG(q); CHECK_BF16(out); CHECK_CONTIG(out);
+  TORCH_CHECK(!(q.has_value() && rope_x.has_value()), "attn_decode: q (rotated) or the QKV projection, not both");
+  const bool fused_rope = slabs_given(q.has_value() ? q : rope_x, rope_slabs, "attn_decode") || rope_x.has_value();
+  CHECK_DEV(out); CHECK_BF16(out); CHECK_CONTIG(out);
+  const at::Tensor& shape = q.has_value() ? *q : out;
+  if (q.has_value()) { CHECK_DEV(*q); CHECK_BF16(*q); CHECK_CONTIG(*q); }
   const bool fp8 = kv_is_fp8(k_cache);
   TORCH_CHECK(fp8 ? kv_is_fp8(v_cache) : (k_cache.scalar_type() == at::kBFloat16 &&
                                           v_cache.scalar_type() == at::kBFloat16),
@@ -472,8 +469,8 @@ void attn_decode(const at::Tensor& q, const at::Tensor& k_cache, const at::Tenso
   CHECK_DEV(k_cache); CHECK_DEV(v_cache); CHECK_CONTIG(k_cache); CHECK_CONTIG(v_cache);
   CHECK_DT(block_tables, at::kInt); CHECK_CONTIG(block_tables); CHECK_DT(seq_lens, at::kInt); CHECK_CONTIG(seq_lens);
   CHECK_DT(o_part, at::kFloat); CHECK_DT(ml_part, at::kFloat); CHECK_CONTIG(o_part); CHECK_CONTIG(ml_part);
-  TORCH_CHECK(q.dim() == 3, "q must be [B, Hq, D]");
-  const int64_t B = q.size(0), Hq = q.size(1), D = q.size(2);
+  TORCH_CHECK(shape.dim() == 3, "q (out when the RoPE is fused) must be [B, Hq, D]");
+  const int64_t B = shape.size(0), Hq = shape.size(1), D = shape.size(2);
   TORCH_CHECK(k_cache.dim() == 4 && k_cache.sizes() == v_cache.sizes() && k_cache.size(3) == D, "cache shape");
   const int64_t Hkv = k_cache.size(1), page = k_cache.size(2);
   TORCH_CHECK(D == 128 && Hq % Hkv == 0, "head_dim must be 128 and Hq % Hkv == 0");
@@ -497,22 +494,19 @@ void attn_decode(const at::Tensor& q, const at::Tensor& k_cache, const at::Tenso
     q8p = static_cast<uint8_t*>(q8->data_ptr());
     sxp = sx->data_ptr<float>();
   }
-  // rope_x: the decode step's RoPE + KV write folded in (q unused, a shape carrier): the QKV
-  // projection as `rope_splits` fp32 split-K slabs [S, B, (Hq+2Hkv)D] or bf16 rows [B, (Hq+2Hkv)D]
   oamd::DecRope rp{};
   const oamd::DecRope* rpp = nullptr;
-  if (rope_x.has_value()) {
+  if (fused_rope) {
     TORCH_CHECK(pos.has_value() && cos_t.has_value() && sin_t.has_value() && slots.has_value(),
                 "fused RoPE needs pos, cos, sin and slots");
     const int64_t ncol = (Hq + 2 * Hkv) * D;
-    CHECK_DEV(*rope_x); CHECK_CONTIG(*rope_x);
-    if (rope_x->scalar_type() == at::kFloat) {
-      TORCH_CHECK(rope_splits >= 1 && rope_x->numel() >= rope_splits * B * ncol, "fused RoPE: slabs too small");
-      rp.xp = rope_x->data_ptr<float>();
-      rp.S = (int)rope_splits;
-      rp.slab = B * ncol;
+    if (rope_slabs.has_value()) {
+      const oamd::Slabs sl = slab_input(*rope_slabs, rope_splits, B, ncol, "attn_decode");
+      rp.xp = sl.p;
+      rp.S = sl.S;
+      rp.slab = sl.stride;
     } else {
-      CHECK_BF16(*rope_x);
+      CHECK_DEV(*rope_x); CHECK_CONTIG(*rope_x); CHECK_BF16(*rope_x);
       TORCH_CHECK(rope_x->dim() == 2 && rope_x->size(0) == B && rope_x->size(1) == ncol, "fused RoPE: qkv [B, ncol]");
       rp.row = ptr<bf16_t>(*rope_x);
       rp.row_stride = rope_x->stride(0);
@@ -536,8 +530,8 @@ void attn_decode(const at::Tensor& q, const at::Tensor& k_cache, const at::Tenso
     rp.v_inv = (float)(1.0 / v_scale);
     rpp = &rp;
   }
-  const c10::hip::HIPGuardMasqueradingAsCUDA g(q.device());
-  RC(oamd::attn_decode(ptr<bf16_t>(q), k_cache.data_ptr(), v_cache.data_ptr(), fp8, (float)k_scale, (float)v_scale,
+  const c10::hip::HIPGuardMasqueradingAsCUDA g(out.device());
+  RC(oamd::attn_decode(optr<bf16_t>(q), k_cache.data_ptr(), v_cache.data_ptr(), fp8, (float)k_scale, (float)v_scale,
                        ptr<int>(block_tables), ptr<int>(seq_lens), ptr<bf16_t>(out), ptr<float>(o_part),
                        ptr<float>(ml_part), (int)B, (int)Hq, (int)Hkv, (int)D, (int)page, (int)block_tables.size(1),
                        (int)num_splits, (float)scale, (int)variant, cur_stream(), q8p, sxp, rpp));
@@ -643,7 +637,7 @@ PYBIND11_MODULE(_C, m) {
   m.doc() = "operator_amd gfx950 kernels";
   m.def("rmsnorm", &rmsnorm, "RMSNorm with optional fused residual add (and split-K slab sum)", pybind11::arg("x"),
         pybind11::arg("residual"), pybind11::arg("w"), pybind11::arg("y"), pybind11::arg("eps"),
-        pybind11::arg("partial") = pybind11::none(), pybind11::arg("splits") = 1, pybind11::arg("tiled_out") = false);
+        pybind11::arg("slabs") = pybind11::none(), pybind11::arg("splits") = 1, pybind11::arg("tiled_out") = false);
   m.def("gemm_xr", &gemm_xr, pybind11::arg("xt"), pybind11::arg("w"), pybind11::arg("y") = pybind11::none(),
         pybind11::arg("p") = pybind11::none(), pybind11::arg("splits") = 1, pybind11::arg("epi") = 1);
   m.def("tile_rows", &tile_rows, pybind11::arg("x"), pybind11::arg("xt"));
@@ -652,13 +646,13 @@ PYBIND11_MODULE(_C, m) {
   m.def("rope_kv", &rope_kv, pybind11::arg("qkv"), pybind11::arg("pos"), pybind11::arg("cos"),
         pybind11::arg("sin"), pybind11::arg("Hq"), pybind11::arg("Hkv"), pybind11::arg("q_out"),
         pybind11::arg("k_out"), pybind11::arg("v_out"), pybind11::arg("k_cache"), pybind11::arg("v_cache"),
-        pybind11::arg("slots"), pybind11::arg("partial") = pybind11::none(), pybind11::arg("splits") = 1,
+        pybind11::arg("slots"), pybind11::arg("slabs") = pybind11::none(), pybind11::arg("splits") = 1,
         pybind11::arg("bias") = pybind11::none(), pybind11::arg("k_scale") = 1.0, pybind11::arg("v_scale") = 1.0);
   m.def("attn_decode", &attn_decode, pybind11::arg("q"), pybind11::arg("k_cache"), pybind11::arg("v_cache"),
         pybind11::arg("block_tables"), pybind11::arg("seq_lens"), pybind11::arg("out"), pybind11::arg("o_part"),
         pybind11::arg("ml_part"), pybind11::arg("num_splits"), pybind11::arg("scale"), pybind11::arg("variant") = 0,
         pybind11::arg("k_scale") = 1.0, pybind11::arg("v_scale") = 1.0, pybind11::arg("q8") = pybind11::none(),
-        pybind11::arg("sx") = pybind11::none(), pybind11::arg("rope_x") = pybind11::none(),
+        pybind11::arg("sx") = pybind11::none(), pybind11::arg("rope_x") = pybind11::none(), pybind11::arg("rope_slabs") = pybind11::none(),
         pybind11::arg("rope_splits") = 1, pybind11::arg("pos") = pybind11::none(), pybind11::arg("cos") = pybind11::none(),
         pybind11::arg("sin") = pybind11::none(), pybind11::arg("slots") = pybind11::none(),
         pybind11::arg("bias") = pybind11::none());

@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "bind_check.h"
 #include "kernels/kernels.h"
 
 namespace {
@@ -74,7 +75,6 @@ class CustomAllReduce {
                           at::Tensor& y, double eps, const c10::optional<at::Tensor>& slabs, int64_t splits,
                           const c10::optional<at::Tensor>& q8, const c10::optional<at::Tensor>& sx, int64_t proto) {
     TORCH_CHECK(opened_ || world_ == 1, "CustomAllReduce: open() the peer handles first");
-    TORCH_CHECK(in.has_value() != slabs.has_value(), "exactly one of in / slabs");
     TORCH_CHECK(q8.has_value() == sx.has_value(), "q8 and sx together");
     auto on_dev = [&](const at::Tensor& t) {
       TORCH_CHECK(t.is_cuda() && t.device().index() == device_ && t.is_contiguous(), "contiguous tensors on this device");
@@ -88,17 +88,13 @@ class CustomAllReduce {
     TORCH_CHECK(w.numel() == hidden, "w [hidden]");
     TORCH_CHECK(hidden % 8 == 0 && hidden <= 16384, "hidden % 8 == 0 and <= 16384");
     TORCH_CHECK(rows * hidden * 2 <= cap_, "size must be <= capacity");
-    const void* ip = nullptr;
-    const float* sp = nullptr;
-    if (in.has_value()) {
+    oamd::Slabs sl;
+    if (slabs_given(in, slabs, "all_reduce_rmsnorm")) {
+      on_dev(*slabs);
+      sl = slab_input(*slabs, splits, rows, hidden, "all_reduce_rmsnorm");
+    } else {
       on_dev(*in);
       TORCH_CHECK(in->scalar_type() == at::kBFloat16 && in->sizes() == residual.sizes(), "in: bf16 [rows, hidden]");
-      ip = in->data_ptr();
-    } else {
-      on_dev(*slabs);
-      TORCH_CHECK(slabs->scalar_type() == at::kFloat && splits >= 1 && slabs->numel() >= splits * rows * hidden,
-                  "slabs: fp32 [splits, rows, hidden]");
-      sp = slabs->data_ptr<float>();
     }
     uint8_t* qp = nullptr;
     float* xp = nullptr;
@@ -113,7 +109,7 @@ class CustomAllReduce {
     }
     const c10::hip::HIPGuardMasqueradingAsCUDA g(residual.device());
     const int rc = oamd::car_all_reduce_rmsnorm(
-        ip, sp, (int)splits, reinterpret_cast<oamd::bf16_t*>(residual.data_ptr()),
+        in.has_value() ? in->data_ptr() : nullptr, sl, reinterpret_cast<oamd::bf16_t*>(residual.data_ptr()),
         reinterpret_cast<const oamd::bf16_t*>(w.data_ptr()), reinterpret_cast<oamd::bf16_t*>(y.data_ptr()), qp, xp,
         (int)rows, (int)hidden, (float)eps, (int)rank_, (int)world_, bases_.data(), (size_t)cap_, (int)blocks_,
         herr_dev_, timeout_s_, (int)proto, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream());

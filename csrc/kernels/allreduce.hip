@@ -345,7 +345,7 @@ __global__ void __launch_bounds__(car::kThreads) allreduce_kernel(const uint4* _
 // the residual add is rounded to bf16, the normalised value is rounded before w.
 // SLABS: the input is S fp32 split-K slabs [S, rows, hidden] of the producing GEMM,
 // summed in slab order and rounded to bf16 on the way into the peers' receive slots
-// (bit-identical to splitk_reduce_fp32 + the bf16 path, one kernel fewer).
+// (bit-identical to splitk_reduce + the bf16 path, one kernel fewer).
 // Q8: also emit the normalised rows as per-row e4m3fn (q8, sx) for the next fp8 GEMM,
 // bit-identical to quantize_fp8(y) — the activation quantization kernel disappears.
 template <int W, int MAXV, bool SLABS, bool Q8, bool TWO, bool LIGHT, bool LL = false>
@@ -379,35 +379,16 @@ __global__ void __launch_bounds__(car::kThreads) ar_rmsnorm_kernel(
 #pragma unroll
   for (int p = 0; p < W; ++p) rs[p] = car::rsrc(peers.base[p]);
   const __amdgpu_buffer_rsrc_t rm = car::rsrc(mine);
-  const int64_t MN = (int64_t)rows * hidden;
+  const int64_t MN = (int64_t)rows * hidden;   // the slab stride (Slabs::stride, checked by the launcher)
   auto load_x = [&](int64_t v) -> uint4 {
     if constexpr (SLABS) {
       const float* pv = slabs + v * 8;
-      f32x4 a0 = *reinterpret_cast<const f32x4*>(pv), a1 = *reinterpret_cast<const f32x4*>(pv + 4);
-      if (S == 2) {   // the usual decode split: both slabs' loads in flight together
-        const f32x4 b0 = *reinterpret_cast<const f32x4*>(pv + MN), b1 = *reinterpret_cast<const f32x4*>(pv + MN + 4);
-        a0 += b0;
-        a1 += b1;
-      } else if (S == 4) {
-        f32x4 bb[3][2];
-#pragma unroll
-        for (int s = 1; s < 4; ++s) {
-          bb[s - 1][0] = *reinterpret_cast<const f32x4*>(pv + s * MN);
-          bb[s - 1][1] = *reinterpret_cast<const f32x4*>(pv + s * MN + 4);
-        }
-#pragma unroll
-        for (int s = 0; s < 3; ++s) {   // slab order
-          a0 += bb[s][0];
-          a1 += bb[s][1];
-        }
-      } else {
-        for (int s = 1; s < S; ++s) {
-          a0 += *reinterpret_cast<const f32x4*>(pv + s * MN);
-          a1 += *reinterpret_cast<const f32x4*>(pv + s * MN + 4);
-        }
-      }
-      return make_uint4(pack_bf2(a0[0], a0[1]), pack_bf2(a0[2], a0[3]), pack_bf2(a1[0], a1[1]),
-                        pack_bf2(a1[2], a1[3]));
+      f32x4 a[2];
+      if (S == 2) slab_sum<2>(pv, S, MN, {0, 4}, a);   // the usual decode splits: every slab's loads in flight together
+      else if (S == 4) slab_sum<4>(pv, S, MN, {0, 4}, a);
+      else slab_sum<0>(pv, S, MN, {0, 4}, a);
+      return make_uint4(pack_bf2(a[0][0], a[0][1]), pack_bf2(a[0][2], a[0][3]), pack_bf2(a[1][0], a[1][1]),
+                        pack_bf2(a[1][2], a[1][3]));
     } else {
       return in[v];
     }
@@ -677,17 +658,17 @@ int car_all_reduce(const void* in, void* out, int64_t bytes, bool bf16, int rank
   return 0;
 }
 
-int car_all_reduce_rmsnorm(const void* in, const float* slabs, int S, bf16_t* residual, const bf16_t* w, bf16_t* y,
+int car_all_reduce_rmsnorm(const void* in, Slabs sl, bf16_t* residual, const bf16_t* w, bf16_t* y,
                            uint8_t* q8, float* sx, int rows, int hidden, float eps, int rank, int world,
                            void* const* bases, size_t cap_bytes, int blocks, uint32_t* herr_dev, double timeout_s,
                            int proto, hipStream_t stream) {
-  if ((slabs == nullptr) == (in == nullptr) || (slabs != nullptr && S < 1)) return -5;
+  if ((sl.p == nullptr) == (in == nullptr) || (sl.p != nullptr && (sl.S < 1 || sl.stride != (int64_t)rows * hidden))) return -5;
   if ((q8 == nullptr) != (sx == nullptr)) return -5;
   if (world < 1 || world > car::kMaxRanks || rank < 0 || rank >= world) return -1;
   if (rows < 1 || hidden < 8 || hidden % 8 != 0 || hidden > car::kThreads * 8 * 4) return -2;
   if ((size_t)rows * hidden * 2 > cap_bytes || cap_bytes % 16 != 0) return -2;
   if (blocks < 1 || blocks > car::kMaxBlocks) return -3;
-  if ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(slabs) | reinterpret_cast<uintptr_t>(residual) |
+  if ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(sl.p) | reinterpret_cast<uintptr_t>(residual) |
        reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(q8)) & 15)
     return -4;
   if (proto < kCarOneShot || proto > kCarLL) return -6;
@@ -699,10 +680,10 @@ int car_all_reduce_rmsnorm(const void* in, const float* slabs, int S, bf16_t* re
   const uint4* i4 = static_cast<const uint4*>(in);
   const uint64_t ticks = timeout_s > 0 ? (uint64_t)(timeout_s * 1e8) : car::kDefaultTimeoutTicks;
   const bool big = hidden > car::kThreads * 8 * 2;
-  const int mode = (slabs != nullptr ? 1 : 0) | (q8 != nullptr ? 2 : 0);
+  const int mode = (sl.p != nullptr ? 1 : 0) | (q8 != nullptr ? 2 : 0);
 #define OAMD_CARK(W, MV, SL, Q, T, L, LLP)                                                                     \
   ar_rmsnorm_kernel<W, MV, SL, Q, T, L, LLP><<<blocks, car::kThreads, 0, stream>>>(                            \
-      i4, slabs, S, residual, w, y, q8, sx, rows, hidden, eps, capvec, rank, peers, herr_dev, ticks)
+      i4, sl.p, sl.S, residual, w, y, q8, sx, rows, hidden, eps, capvec, rank, peers, herr_dev, ticks)
 #define OAMD_CARP(W, MV, SL, Q)                                                                                \
   if (proto == kCarTwoShot) OAMD_CARK(W, MV, SL, Q, (W > 1), true, false);                                     \
   else if (proto == kCarOneShot) OAMD_CARK(W, MV, SL, Q, false, true, false);                                  \

@@ -142,17 +142,9 @@ template <int SC>
 __device__ __forceinline__ f32x4 qkv4(const DecRope& r, int b, int ncol, int col) {
   f32x4 a;
   if (r.xp != nullptr) {
-    const float* p = r.xp + (int64_t)b * ncol + col;
-    a = *reinterpret_cast<const f32x4*>(p);
-    if constexpr (SC > 1 && SC <= 8) {
-      f32x4 t[SC - 1];
-#pragma unroll
-      for (int k = 1; k < SC; ++k) t[k - 1] = *reinterpret_cast<const f32x4*>(p + k * r.slab);
-#pragma unroll
-      for (int k = 1; k < SC; ++k) a += t[k - 1];
-    } else if constexpr (SC == 9) {
-      for (int k = 1; k < r.S; ++k) a += *reinterpret_cast<const f32x4*>(p + k * r.slab);
-    }
+    f32x4 s4[1];
+    slab_sum<(SC == 9 ? 0 : SC)>(r.xp + (int64_t)b * ncol + col, r.S, r.slab, {0}, s4);
+    a = s4[0];
   } else {
     const uint2 u = *reinterpret_cast<const uint2*>(r.row + (int64_t)b * r.row_stride + col);
     a = f32x4{__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),

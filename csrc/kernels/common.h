@@ -81,6 +81,33 @@ __device__ __forceinline__ float block_sum(float v, float* scratch) {
   return t;
 }
 
+// The split-K hand-off, stated once: a[v] = the sum, in slab order, over the S fp32 slabs
+// (`slab` floats apart) of the 4 floats at pr + off[v]. The caller rounds the sum to bf16
+// once. SC > 0: the slab count is known at compile time and every slab load is issued
+// before the first add (a runtime-trip-count loop waits for each load in turn: S dependent
+// L2/HBM round trips); SC == 0: runtime S, one slab per trip.
+template <int SC, int NV>
+__device__ __forceinline__ void slab_sum(const float* pr, int S, int64_t slab, const int (&off)[NV],
+                                         f32x4 (&a)[NV]) {
+#pragma unroll
+  for (int v = 0; v < NV; ++v) a[v] = *reinterpret_cast<const f32x4*>(pr + off[v]);
+  if constexpr (SC > 1) {
+    f32x4 t[SC - 1][NV];
+#pragma unroll
+    for (int s = 1; s < SC; ++s)
+#pragma unroll
+      for (int v = 0; v < NV; ++v) t[s - 1][v] = *reinterpret_cast<const f32x4*>(pr + s * slab + off[v]);
+#pragma unroll
+    for (int s = 1; s < SC; ++s)
+#pragma unroll
+      for (int v = 0; v < NV; ++v) a[v] += t[s - 1][v];
+  } else if constexpr (SC == 0) {
+    for (int s = 1; s < S; ++s)
+#pragma unroll
+      for (int v = 0; v < NV; ++v) a[v] += *reinterpret_cast<const f32x4*>(pr + s * slab + off[v]);
+  }
+}
+
 // Bijective XCD-aware block remap (cdna_hip_programming.md §5 "XCD swizzle must
 // be bijective"): consecutive logical tiles land on the same XCD (same L2).
 __device__ __forceinline__ int xcd_remap(int orig, int nwg) {

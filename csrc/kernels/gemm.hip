@@ -231,11 +231,11 @@ __global__ void __launch_bounds__(kWaves * 64, NS == 2 ? 2 : 1) gemm_tn_kernel(c
 __global__ void gemm_splitk_reduce_kernel(const float* __restrict__ P, bf16_t* __restrict__ Y, int64_t MN, int S) {
   const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   if (i >= MN) return;
-  f32x4 a = *reinterpret_cast<const f32x4*>(P + i);
-  for (int s = 1; s < S; ++s) a += *reinterpret_cast<const f32x4*>(P + s * MN + i);
+  f32x4 a[1];
+  slab_sum<0>(P + i, S, MN, {0}, a);
   uint2 o;
-  o.x = pack_bf2(a[0], a[1]);
-  o.y = pack_bf2(a[2], a[3]);
+  o.x = pack_bf2(a[0][0], a[0][1]);
+  o.y = pack_bf2(a[0][2], a[0][3]);
   *reinterpret_cast<uint2*>(Y + i) = o;
 }
 
@@ -303,12 +303,7 @@ int gemm_decode(const bf16_t* X, const bf16_t* W, bf16_t* Y, float* P, int M, in
 #undef OAMD_GEMM2
 #undef OAMD_GEMM3
   OAMD_LAUNCH_CHECK();
-  if (S > 1 && Y != nullptr) {  // Y == nullptr: the consumer sums the slabs (rmsnorm)
-    const int64_t MN = (int64_t)M * N;
-    const int64_t threads = MN / 4;
-    gemm_splitk_reduce_kernel<<<(threads + 255) / 256, 256, 0, stream>>>(P, Y, MN, S);
-    OAMD_LAUNCH_CHECK();
-  }
+  if (S > 1 && Y != nullptr) return splitk_reduce(P, Y, (int64_t)M * N, S, stream);  // else the consumer sums the slabs
   return 0;
 }
 

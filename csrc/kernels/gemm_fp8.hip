@@ -155,9 +155,8 @@ __global__ void __launch_bounds__(f8::kWaves * 64, 1)
 // row quantized is bf16(bf16(silu(bf16 g)) * bf16 u) — the SwiGLU and the down
 // projection's input quantization in one kernel.
 // P (SILU only): the gate|up rows are S fp32 split-K slabs [S, M, 2K] instead of bf16 `x`;
-// they are summed in slab order and bf16-rounded first (== splitk_reduce_fp32 then SILU).
-// SC (SILU with slabs): compile-time slab count, so every slab load of an element is issued
-// before the first add (0: runtime S, one slab per loop trip).
+// they are summed in slab order and bf16-rounded first (== splitk_reduce then SILU).
+// SC (SILU with slabs): compile-time slab count (0: runtime S), common.h slab_sum.
 template <int MAXV, bool SILU, int SC = 0>
 __global__ void __launch_bounds__(256) quantize_rows_reg_kernel(const bf16_t* __restrict__ x, uint8_t* __restrict__ q,
                                                                 float* __restrict__ sx, int K, int64_t ld,
@@ -176,42 +175,16 @@ __global__ void __launch_bounds__(256) quantize_rows_reg_kernel(const bf16_t* __
         const int c = (vi >> 3) * 128 + (vi & 7) * 8;   // 64-feature blocks: gate then up
         u16x8 gv, uv;
         if (P != nullptr) {
-          const int64_t MN = (int64_t)gridDim.x * 2 * K;
+          f32x4 a[4];   // gate 0..3, 4..7, up 0..3, 4..7
+          const int64_t MN = gridDim.x * (2 * (int64_t)K);   // the slab stride (Slabs::stride, checked by the launcher)
           const float* pr = P + m * 2 * K + c;
-          f32x4 g0 = *reinterpret_cast<const f32x4*>(pr), g1 = *reinterpret_cast<const f32x4*>(pr + 4);
-          f32x4 u0 = *reinterpret_cast<const f32x4*>(pr + 64), u1 = *reinterpret_cast<const f32x4*>(pr + 68);
-          if constexpr (SC > 1) {
-            f32x4 sl[SC - 1][4];
-#pragma unroll
-            for (int s = 1; s < SC; ++s) {
-              const float* ps = pr + s * MN;
-              sl[s - 1][0] = *reinterpret_cast<const f32x4*>(ps);
-              sl[s - 1][1] = *reinterpret_cast<const f32x4*>(ps + 4);
-              sl[s - 1][2] = *reinterpret_cast<const f32x4*>(ps + 64);
-              sl[s - 1][3] = *reinterpret_cast<const f32x4*>(ps + 68);
-            }
-#pragma unroll
-            for (int s = 1; s < SC; ++s) {   // slab order, as splitk_reduce_fp32
-              g0 += sl[s - 1][0];
-              g1 += sl[s - 1][1];
-              u0 += sl[s - 1][2];
-              u1 += sl[s - 1][3];
-            }
-          } else if constexpr (SC == 0) {
-            for (int s = 1; s < S; ++s) {
-              const float* ps = pr + s * MN;
-              g0 += *reinterpret_cast<const f32x4*>(ps);
-              g1 += *reinterpret_cast<const f32x4*>(ps + 4);
-              u0 += *reinterpret_cast<const f32x4*>(ps + 64);
-              u1 += *reinterpret_cast<const f32x4*>(ps + 68);
-            }
-          }
+          slab_sum<SC>(pr, S, MN, {0, 4, 64, 68}, a);
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            gv[j] = f2bf(g0[j]);
-            gv[j + 4] = f2bf(g1[j]);
-            uv[j] = f2bf(u0[j]);
-            uv[j + 4] = f2bf(u1[j]);
+            gv[j] = f2bf(a[0][j]);
+            gv[j + 4] = f2bf(a[1][j]);
+            uv[j] = f2bf(a[2][j]);
+            uv[j + 4] = f2bf(a[3][j]);
           }
         } else {
           gv = *reinterpret_cast<const u16x8*>(xr + c);
@@ -308,19 +281,19 @@ int quantize_fp8_rows(const bf16_t* x, uint8_t* q, float* sx, int M, int K, int6
   return 0;
 }
 
-int silu_quantize_fp8(const bf16_t* gu, const float* P, int S, uint8_t* q, float* sx, int M, int inter, int64_t ld,
+int silu_quantize_fp8(const bf16_t* gu, Slabs sl, uint8_t* q, float* sx, int M, int inter, int64_t ld,
                       hipStream_t stream) {
   if (M == 0) return 0;
-  if (inter % 64 != 0 || (gu == nullptr) == (P == nullptr) || S < 1) return -1;
+  if (inter % 64 != 0 || (gu == nullptr) == (sl.p == nullptr) || (sl.p != nullptr && (sl.S < 1 || sl.stride != (int64_t)M * 2 * inter))) return -1;
   const int nv = inter / 8;
-  const int sc = P == nullptr ? 1 : S;
+  const int sc = sl.p == nullptr ? 1 : sl.S;
 #define OAMD_SQ(MV)                                                                                       \
   switch (sc) {                                                                                           \
-    case 1: quantize_rows_reg_kernel<MV, true, 1><<<M, 256, 0, stream>>>(gu, q, sx, inter, ld, P, S); break; \
-    case 2: quantize_rows_reg_kernel<MV, true, 2><<<M, 256, 0, stream>>>(gu, q, sx, inter, ld, P, S); break; \
-    case 4: quantize_rows_reg_kernel<MV, true, 4><<<M, 256, 0, stream>>>(gu, q, sx, inter, ld, P, S); break; \
-    case 8: quantize_rows_reg_kernel<MV, true, 8><<<M, 256, 0, stream>>>(gu, q, sx, inter, ld, P, S); break; \
-    default: quantize_rows_reg_kernel<MV, true, 0><<<M, 256, 0, stream>>>(gu, q, sx, inter, ld, P, S); break; \
+    case 1: quantize_rows_reg_kernel<MV, true, 1><<<M, 256, 0, stream>>>(gu, q, sx, inter, ld, sl.p, sl.S); break; \
+    case 2: quantize_rows_reg_kernel<MV, true, 2><<<M, 256, 0, stream>>>(gu, q, sx, inter, ld, sl.p, sl.S); break; \
+    case 4: quantize_rows_reg_kernel<MV, true, 4><<<M, 256, 0, stream>>>(gu, q, sx, inter, ld, sl.p, sl.S); break; \
+    case 8: quantize_rows_reg_kernel<MV, true, 8><<<M, 256, 0, stream>>>(gu, q, sx, inter, ld, sl.p, sl.S); break; \
+    default: quantize_rows_reg_kernel<MV, true, 0><<<M, 256, 0, stream>>>(gu, q, sx, inter, ld, sl.p, sl.S); break; \
   }
   if (nv <= 256 * 2) { OAMD_SQ(2) }
   else if (nv <= 256 * 4) { OAMD_SQ(4) }
@@ -329,17 +302,6 @@ int silu_quantize_fp8(const bf16_t* gu, const float* P, int S, uint8_t* q, float
 #undef OAMD_SQ
   OAMD_LAUNCH_CHECK();
   return 0;
-}
-
-__global__ void splitk_reduce_fp32_kernel(const float* __restrict__ P, bf16_t* __restrict__ Y, int64_t MN, int S) {
-  const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-  if (i >= MN) return;
-  f32x4 a = *reinterpret_cast<const f32x4*>(P + i);
-  for (int s = 1; s < S; ++s) a += *reinterpret_cast<const f32x4*>(P + s * MN + i);
-  uint2 o;
-  o.x = pack_bf2(a[0], a[1]);
-  o.y = pack_bf2(a[2], a[3]);
-  *reinterpret_cast<uint2*>(Y + i) = o;
 }
 
 int gemm_fp8(const uint8_t* X, const uint8_t* W, const float* sx, const float* sw, bf16_t* Y, float* P, int M,
@@ -366,9 +328,7 @@ int gemm_fp8(const uint8_t* X, const uint8_t* W, const float* sx, const float* s
 #undef OAMD_G8
   OAMD_LAUNCH_CHECK();
   if (S > 1 && Y != nullptr) {   // Y == nullptr: the consumer sums the slabs
-    const int64_t MN = (int64_t)M * N;
-    splitk_reduce_fp32_kernel<<<(MN / 4 + 255) / 256, 256, 0, stream>>>(P, Y, MN, S);
-    OAMD_LAUNCH_CHECK();
+    return splitk_reduce(P, Y, (int64_t)M * N, S, stream);
   }
   return 0;
 }

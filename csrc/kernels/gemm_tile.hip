@@ -880,17 +880,13 @@ __global__ void splitk_silu_reduce_kernel(const float* __restrict__ P, bf16_t* _
   const int m = (int)(i / NO), f = (int)(i % NO);
   const int col = (f >> 6) * 128 + (f & 63);
   const int64_t MN = (int64_t)M * N;
-  const float* pr = P + (int64_t)m * N + col;
-  f32x4 g = *reinterpret_cast<const f32x4*>(pr), u = *reinterpret_cast<const f32x4*>(pr + 64);
-  for (int s = 1; s < S; ++s) {
-    g += *reinterpret_cast<const f32x4*>(pr + s * MN);
-    u += *reinterpret_cast<const f32x4*>(pr + s * MN + 64);
-  }
+  f32x4 gu[2];   // gate, up
+  slab_sum<0>(P + (int64_t)m * N + col, S, MN, {0, 64}, gu);
   f32x4 o;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const float gg = bf2f(f2bf(g[r]));
-    const float uu = bf2f(f2bf(u[r]));
+    const float gg = bf2f(f2bf(gu[0][r]));
+    const float uu = bf2f(f2bf(gu[1][r]));
     o[r] = bf2f(f2bf(gg / (1.f + __expf(-gg)))) * uu;
   }
   *reinterpret_cast<uint2*>(Y + (int64_t)m * ldy + f) = pack4(o);

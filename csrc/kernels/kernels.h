@@ -9,10 +9,18 @@
 namespace oamd {
 typedef uint16_t bf16_t;
 
+// A split-K GEMM's output handed to its consumer unreduced: S fp32 slabs [S][rows][cols], slab s at
+// p + s * stride; the consumer reads bf16(sum over s, in slab order) in place of a bf16 input row
+// (common.h slab_sum). p == nullptr: no slabs, the consumer reads its bf16 input.
+struct Slabs {
+  const float* p = nullptr;
+  int S = 1;
+  int64_t stride = 0;
+};
+
 // ---- explanation-model ops ----
 int rmsnorm(const bf16_t* x, bf16_t* residual, const bf16_t* w, bf16_t* y, int rows, int hidden,
-            int64_t x_stride, int64_t r_stride, int64_t y_stride, float eps, const float* xp, int S,
-            hipStream_t stream);
+            int64_t x_stride, int64_t r_stride, int64_t y_stride, float eps, Slabs sl, hipStream_t stream);
 int silu_mul(const bf16_t* gu, bf16_t* out, int64_t rows, int inter, int block, int64_t in_stride,
              int64_t out_stride, hipStream_t stream);
 // Decode-step bookkeeping (norm_act.hip): cache slots + sampler positions of the step's tokens,
@@ -26,7 +34,7 @@ int embedding(const int64_t* ids, const bf16_t* table, bf16_t* out, int tokens, 
 int rope_kv(const bf16_t* qkv, int64_t qkv_stride, const int64_t* pos, const float* cos_t,
             const float* sin_t, int tokens, int Hq, int Hkv, int head_dim, bf16_t* q_out,
             bf16_t* k_out, bf16_t* v_out, void* k_cache, void* v_cache, const int64_t* slots,
-            int page_size, int64_t max_pos, const float* xp, int S, const bf16_t* bias,
+            int page_size, int64_t max_pos, Slabs sl, const bf16_t* bias,
             bool fp8_cache, float k_scale, float v_scale, hipStream_t stream);  // cache: bf16 or e4m3fn
 // Y[M,N] = X[M,K] W[N,K]^T for decode buckets (M a multiple of the BM-row tile, BM in {64,128,256}); S-way split-K
 // (S | 8) with fp32 slabs P[S][M][N] reduced into Y; BN in {64, 128} columns per tile.
@@ -75,8 +83,8 @@ int gemm_fp8(const uint8_t* X, const uint8_t* W, const float* sx, const float* s
 int quantize_fp8_rows(const bf16_t* x, uint8_t* q, float* sx, int M, int K, int64_t ld, hipStream_t stream);
 // Fused SwiGLU + per-row e4m3fn quantization of the 64-feature-interleaved gate|up rows [M, 2 inter]
 // (inter % 64 == 0, <= 16384): q [M, inter], sx [M].
-// gu == nullptr: the gate|up rows are the S fp32 split-K slabs P [S, M, 2 inter] (summed, bf16-rounded).
-int silu_quantize_fp8(const bf16_t* gu, const float* P, int S, uint8_t* q, float* sx, int M, int inter, int64_t ld,
+// gu == nullptr: the gate|up rows are the split-K slabs sl [S, M, 2 inter] (summed, bf16-rounded).
+int silu_quantize_fp8(const bf16_t* gu, Slabs sl, uint8_t* q, float* sx, int M, int inter, int64_t ld,
                       hipStream_t stream);
 
 // Pattern-event scoring + per-doc ranking / summary (N5), see score.hip.
@@ -91,6 +99,8 @@ int score_events(const int64_t* keys, const int* hit_doc, const int* doc_ptr, in
 // holding a sequence's last token writes that token's rotated K and its V into the cache.
 // Row b of the projection is bf16(sum of S fp32 split-K slabs [S][rows][ncol] (+ bias)) or
 // a bf16 row (+ bias), ncol = (Hq + 2 Hkv) * 128 -- the numerics of rope_kv.
+// (xp / S / slab are a Slabs spelled out: this struct is a kernel argument, and moving the three
+// fields together changes the SGPR count of every fused-RoPE attn_decode_kernel.)
 struct DecRope {
   const float* xp;          // split-K slabs, or nullptr
   const bf16_t* row;        // bf16 rows [rows][row_stride] when xp == nullptr
@@ -145,12 +155,12 @@ int car_error(const uint32_t* host);
 int car_reset(void* base, size_t bytes, uint32_t* host);
 // Fused one-shot all-reduce + residual add + RMSNorm (bf16 rows of `hidden`, hidden % 8 == 0, <= 16384):
 // residual += bf16(sum over ranks of in); y = rmsnorm(residual) * w. Exactly one of `in` (bf16 rows) and
-// `slabs` (S fp32 split-K slabs [S, rows, hidden], summed then bf16-rounded) is non-null; q8/sx non-null
+// `sl` (split-K slabs [S, rows, hidden], summed then bf16-rounded) is given; q8/sx non-null
 // also emit per-row e4m3fn of y (== quantize_fp8_rows(y)).
 // all-reduce protocols (allreduce.hip): one-shot / two-shot (reduce-scatter + all-gather)
 // with sc0 sc1 hand-offs, and the original system-fence one-shot (A/B)
 constexpr int kCarOneShot = 0, kCarTwoShot = 1, kCarOneShotFence = 2, kCarLL = 3;
-int car_all_reduce_rmsnorm(const void* in, const float* slabs, int S, bf16_t* residual, const bf16_t* w, bf16_t* y,
+int car_all_reduce_rmsnorm(const void* in, Slabs sl, bf16_t* residual, const bf16_t* w, bf16_t* y,
                            uint8_t* q8, float* sx, int rows, int hidden, float eps, int rank, int world,
                            void* const* bases, size_t cap_bytes, int blocks, uint32_t* herr_dev, double timeout_s,
                            int proto, hipStream_t stream);

@@ -14,16 +14,13 @@ namespace oamd {
 // fp32 split-K slabs xp[s * slab + row * hidden + c] written by gemm_decode —
 // the GEMM's reduction pass is folded into this kernel (same numerics: the
 // projection output is rounded to bf16 once, then added to the residual).
-// SC = compile-time slab count (0: runtime S) so the S slab loads of a vector are
-// all issued before the first add (a runtime-trip-count loop waits for each load
-// in turn: S dependent L2/HBM round trips per vector).
+// SC = compile-time slab count (0: runtime S), common.h slab_sum.
 template <int NT, int MAXV, int SC>
 __global__ void __launch_bounds__(NT) rmsnorm_kernel(
     const bf16_t* __restrict__ x, bf16_t* __restrict__ residual,
     const bf16_t* __restrict__ w, bf16_t* __restrict__ y, int hidden,
     int64_t x_stride, int64_t r_stride, int64_t y_stride, float eps,
     const float* __restrict__ xp, int S_rt, int64_t slab) {
-  const int S = SC > 0 ? SC : S_rt;
   __shared__ float scratch[NT / 64];
   const int row = blockIdx.x;
   const int nvec = hidden >> 3;
@@ -37,30 +34,12 @@ __global__ void __launch_bounds__(NT) rmsnorm_kernel(
     if (vi < nvec) {
       u16x8 a;
       if (xp) {
-        const float* pr = xp + (int64_t)row * hidden + vi * 8;
-        f32x4 lo = *reinterpret_cast<const f32x4*>(pr), hi = *reinterpret_cast<const f32x4*>(pr + 4);
-        if constexpr (SC > 0) {
-          f32x4 pl[SC > 1 ? SC - 1 : 1], ph[SC > 1 ? SC - 1 : 1];
-#pragma unroll
-          for (int sp = 1; sp < SC; ++sp) {
-            pl[sp - 1] = *reinterpret_cast<const f32x4*>(pr + sp * slab);
-            ph[sp - 1] = *reinterpret_cast<const f32x4*>(pr + sp * slab + 4);
-          }
-#pragma unroll
-          for (int sp = 1; sp < SC; ++sp) {
-            lo += pl[sp - 1];
-            hi += ph[sp - 1];
-          }
-        } else {
-          for (int sp = 1; sp < S; ++sp) {
-            lo += *reinterpret_cast<const f32x4*>(pr + sp * slab);
-            hi += *reinterpret_cast<const f32x4*>(pr + sp * slab + 4);
-          }
-        }
+        f32x4 s4[2];
+        slab_sum<SC>(xp + (int64_t)row * hidden + vi * 8, S_rt, slab, {0, 4}, s4);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          a[j] = f2bf(lo[j]);
-          a[4 + j] = f2bf(hi[j]);
+          a[j] = f2bf(s4[0][j]);
+          a[4 + j] = f2bf(s4[1][j]);
         }
       } else {
         a = xr[vi];
@@ -120,27 +99,26 @@ __global__ void __launch_bounds__(NT) rmsnorm_kernel(
 
 int rmsnorm(const bf16_t* x, bf16_t* residual, const bf16_t* w, bf16_t* y,
             int rows, int hidden, int64_t x_stride, int64_t r_stride,
-            int64_t y_stride, float eps, const float* xp, int S, hipStream_t stream) {
+            int64_t y_stride, float eps, Slabs sl, hipStream_t stream) {
   if (rows == 0) return 0;
   constexpr int NT = 256;
   const int nvec = hidden / 8;
-  const int64_t slab = (int64_t)rows * hidden;
-  const int sc = xp == nullptr ? 1 : S;
+  const int sc = sl.p == nullptr ? 1 : sl.S;
   // split-K slab sums of rows up to 4096 wide: 512 threads, one vector each, so a row's
   // slab loads all leave in one round (OAMD_RMS_WIDE=0: 256 threads x 2 vectors)
   static const bool wide = [] { const char* e = getenv("OAMD_RMS_WIDE"); return !(e && e[0] == '0'); }();
-  if (wide && xp != nullptr && sc > 1 && nvec > NT && nvec <= 2 * NT) {
+  if (wide && sl.p != nullptr && sc > 1 && nvec > NT && nvec <= 2 * NT) {
     switch (sc) {
-      case 2: rmsnorm_kernel<2 * NT, 1, 2><<<rows, 2 * NT, 0, stream>>>(x, residual, w, y, hidden, x_stride, r_stride, y_stride, eps, xp, S, slab); break;
-      case 4: rmsnorm_kernel<2 * NT, 1, 4><<<rows, 2 * NT, 0, stream>>>(x, residual, w, y, hidden, x_stride, r_stride, y_stride, eps, xp, S, slab); break;
-      case 8: rmsnorm_kernel<2 * NT, 1, 8><<<rows, 2 * NT, 0, stream>>>(x, residual, w, y, hidden, x_stride, r_stride, y_stride, eps, xp, S, slab); break;
-      default: rmsnorm_kernel<2 * NT, 1, 0><<<rows, 2 * NT, 0, stream>>>(x, residual, w, y, hidden, x_stride, r_stride, y_stride, eps, xp, S, slab); break;
+      case 2: rmsnorm_kernel<2 * NT, 1, 2><<<rows, 2 * NT, 0, stream>>>(x, residual, w, y, hidden, x_stride, r_stride, y_stride, eps, sl.p, sl.S, sl.stride); break;
+      case 4: rmsnorm_kernel<2 * NT, 1, 4><<<rows, 2 * NT, 0, stream>>>(x, residual, w, y, hidden, x_stride, r_stride, y_stride, eps, sl.p, sl.S, sl.stride); break;
+      case 8: rmsnorm_kernel<2 * NT, 1, 8><<<rows, 2 * NT, 0, stream>>>(x, residual, w, y, hidden, x_stride, r_stride, y_stride, eps, sl.p, sl.S, sl.stride); break;
+      default: rmsnorm_kernel<2 * NT, 1, 0><<<rows, 2 * NT, 0, stream>>>(x, residual, w, y, hidden, x_stride, r_stride, y_stride, eps, sl.p, sl.S, sl.stride); break;
     }
     OAMD_LAUNCH_CHECK();
     return 0;
   }
 #define OAMD_RMS(MV, SCC) \
-  rmsnorm_kernel<NT, MV, SCC><<<rows, NT, 0, stream>>>(x, residual, w, y, hidden, x_stride, r_stride, y_stride, eps, xp, S, slab)
+  rmsnorm_kernel<NT, MV, SCC><<<rows, NT, 0, stream>>>(x, residual, w, y, hidden, x_stride, r_stride, y_stride, eps, sl.p, sl.S, sl.stride)
 #define OAMD_RMS_S(MV)                  \
   switch (sc) {                         \
     case 1: OAMD_RMS(MV, 1); break;     \

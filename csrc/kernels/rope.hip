@@ -68,50 +68,30 @@ __global__ void __launch_bounds__(NI) rope_kv_kernel(
   // rounding of the sum of S fp32 split-K slabs of the QKV projection
   auto ld8 = [&](int col) -> u16x8 {
     if (!xp && !bias) return *reinterpret_cast<const u16x8*>(row + col);
-    f32x4 lo, hi;
+    f32x4 a[2];   // a[0] = values 0..3, a[1] = values 4..7
     if (xp) {
-      const float* pr = xp + (int64_t)t * ncol + col;
-      lo = *reinterpret_cast<const f32x4*>(pr);
-      hi = *reinterpret_cast<const f32x4*>(pr + 4);
-      if constexpr (SC > 1) {
-        f32x4 pl[SC - 1], ph[SC - 1];
-#pragma unroll
-        for (int sp = 1; sp < SC; ++sp) {
-          pl[sp - 1] = *reinterpret_cast<const f32x4*>(pr + sp * slab);
-          ph[sp - 1] = *reinterpret_cast<const f32x4*>(pr + sp * slab + 4);
-        }
-#pragma unroll
-        for (int sp = 1; sp < SC; ++sp) {
-          lo += pl[sp - 1];
-          hi += ph[sp - 1];
-        }
-      } else if constexpr (SC == 0) {
-        for (int sp = 1; sp < S; ++sp) {
-          lo += *reinterpret_cast<const f32x4*>(pr + sp * slab);
-          hi += *reinterpret_cast<const f32x4*>(pr + sp * slab + 4);
-        }
-      }
+      slab_sum<SC>(xp + (int64_t)t * ncol + col, S, slab, {0, 4}, a);
     } else {
       const u16x8 r = *reinterpret_cast<const u16x8*>(row + col);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        lo[j] = bf2f(r[j]);
-        hi[j] = bf2f(r[4 + j]);
+        a[0][j] = bf2f(r[j]);
+        a[1][j] = bf2f(r[4 + j]);
       }
     }
     if (bias) {
       const u16x8 bb = *reinterpret_cast<const u16x8*>(bias + col);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        lo[j] += bf2f(bb[j]);
-        hi[j] += bf2f(bb[4 + j]);
+        a[0][j] += bf2f(bb[j]);
+        a[1][j] += bf2f(bb[4 + j]);
       }
     }
     u16x8 o;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      o[j] = f2bf(lo[j]);
-      o[4 + j] = f2bf(hi[j]);
+      o[j] = f2bf(a[0][j]);
+      o[4 + j] = f2bf(a[1][j]);
     }
     return o;
   };
@@ -185,24 +165,23 @@ __global__ void __launch_bounds__(NI) rope_kv_kernel(
 int rope_kv(const bf16_t* qkv, int64_t qkv_stride, const int64_t* pos, const float* cos_t,
             const float* sin_t, int tokens, int Hq, int Hkv, int head_dim, bf16_t* q_out,
             bf16_t* k_out, bf16_t* v_out, void* k_cache, void* v_cache,
-            const int64_t* slots, int page_size, int64_t max_pos, const float* xp, int S,
+            const int64_t* slots, int page_size, int64_t max_pos, Slabs sl,
             const bf16_t* bias, bool fp8_cache, float k_scale, float v_scale, hipStream_t stream) {
   if (tokens == 0) return 0;
   if (head_dim != 128) return -1;
-  const int64_t slab = (int64_t)tokens * (Hq + 2 * Hkv) * head_dim;
   const int items = (Hq + Hkv) * (head_dim / 16) + Hkv * (head_dim / 8);
   static const int ni = [] { const char* e = getenv("OAMD_ROPE_ITEMS"); return e && e[0] == '6' ? 64 : 256; }();   // OAMD_ROPE_ITEMS=64: one-wave workgroups
   const dim3 grid(tokens, (items + ni - 1) / ni);
-  const int sc = xp == nullptr ? 1 : S;
+  const int sc = sl.p == nullptr ? 1 : sl.S;
 #define OAMD_ROPE(KVT, SCC, KI, VI)                                                                              \
   if (ni == 256)                                                                                                 \
     rope_kv_kernel<128, KVT, SCC, 256><<<grid, 256, 0, stream>>>(                                                \
         qkv, qkv_stride, pos, cos_t, sin_t, Hq, Hkv, q_out, k_out, v_out, static_cast<KVT*>(k_cache),          \
-        static_cast<KVT*>(v_cache), slots, page_size, max_pos, xp, S, slab, bias, KI, VI);                      \
+        static_cast<KVT*>(v_cache), slots, page_size, max_pos, sl.p, sl.S, sl.stride, bias, KI, VI);                      \
   else                                                                                                           \
     rope_kv_kernel<128, KVT, SCC><<<grid, kRopeItems, 0, stream>>>(                                             \
         qkv, qkv_stride, pos, cos_t, sin_t, Hq, Hkv, q_out, k_out, v_out, static_cast<KVT*>(k_cache),          \
-        static_cast<KVT*>(v_cache), slots, page_size, max_pos, xp, S, slab, bias, KI, VI)
+        static_cast<KVT*>(v_cache), slots, page_size, max_pos, sl.p, sl.S, sl.stride, bias, KI, VI)
 #define OAMD_ROPE_S(KVT, KI, VI)                   \
   switch (sc) {                                    \
     case 1: OAMD_ROPE(KVT, 1, KI, VI); break;      \

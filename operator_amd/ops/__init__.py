@@ -38,6 +38,12 @@ DECODE_TARGET_BLOCKS = int(os.environ.get("OAMD_DECODE_TARGET_BLOCKS", "256"))
 DECODE_ATTN_VARIANT = int(os.environ.get("OAMD_DECODE_ATTN_VARIANT", "0"))
 
 
+def _input_or_slabs(x):
+    """``(bf16 input, slabs, splits)`` as the bindings take a consumer's input: exactly one of the
+    first two (:class:`SplitK`: the slabs, summed inside the kernel)."""
+    return (None, x.p, x.S) if isinstance(x, SplitK) else (x, None, 1)
+
+
 def rmsnorm(x, w: torch.Tensor, eps: float, residual: torch.Tensor | None = None,
             out: torch.Tensor | None = None) -> torch.Tensor:
     """RMSNorm; if ``residual`` is given it is updated in place to x + residual first.
@@ -45,7 +51,7 @@ def rmsnorm(x, w: torch.Tensor, eps: float, residual: torch.Tensor | None = None
     if isinstance(x, SplitK):
         M, N = x.shape
         y = out if out is not None else torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
-        kernels().rmsnorm(y, residual, w, y, eps, x.p, x.S)  # y doubles as the shape carrier
+        kernels().rmsnorm(None, residual, w, y, eps, x.p, x.S)
         return y
     if not x.is_cuda:
         y, r = reference.rmsnorm(x, w, eps, residual)
@@ -98,17 +104,8 @@ def rope_kv(qkv: torch.Tensor, pos: torch.Tensor, cos: torch.Tensor, sin: torch.
 
     Returns (q [T,Hq,D], k [T,Hkv,D] | None, v [T,Hkv,D] | None).
     """
-    if isinstance(qkv, SplitK):
-        T = qkv.shape[0]
-        D = cos.shape[1] * 2
-        dev = qkv.device
-        q = q_out if q_out is not None else torch.empty(T, Hq, D, dtype=torch.bfloat16, device=dev)
-        k = torch.empty(T, Hkv, D, dtype=torch.bfloat16, device=dev) if want_kv else None
-        v = torch.empty(T, Hkv, D, dtype=torch.bfloat16, device=dev) if want_kv else None
-        kernels().rope_kv(q, pos, cos, sin, Hq, Hkv, q, k, v, k_cache, v_cache, slots, qkv.p, qkv.S, bias,
-                          k_scale, v_scale)
-        return q, k, v
-    if not qkv.is_cuda:
+    slabs = isinstance(qkv, SplitK)
+    if not slabs and not qkv.is_cuda:
         if bias is not None:
             qkv = (qkv.float() + bias.float()).to(qkv.dtype)
         q, k, v = reference.rope_kv(qkv, pos, cos, sin, Hq, Hkv, k_cache, v_cache, slots, k_scale, v_scale)
@@ -118,10 +115,12 @@ def rope_kv(qkv: torch.Tensor, pos: torch.Tensor, cos: torch.Tensor, sin: torch.
         return q, (k if want_kv else None), (v if want_kv else None)
     T = qkv.shape[0]
     D = cos.shape[1] * 2
-    q = q_out if q_out is not None else torch.empty(T, Hq, D, dtype=qkv.dtype, device=qkv.device)
-    k = torch.empty(T, Hkv, D, dtype=qkv.dtype, device=qkv.device) if want_kv else None
-    v = torch.empty(T, Hkv, D, dtype=qkv.dtype, device=qkv.device) if want_kv else None
-    kernels().rope_kv(qkv, pos, cos, sin, Hq, Hkv, q, k, v, k_cache, v_cache, slots, None, 1, bias, k_scale, v_scale)
+    dt, dev = torch.bfloat16 if slabs else qkv.dtype, qkv.device
+    q = q_out if q_out is not None else torch.empty(T, Hq, D, dtype=dt, device=dev)
+    k = torch.empty(T, Hkv, D, dtype=dt, device=dev) if want_kv else None
+    v = torch.empty(T, Hkv, D, dtype=dt, device=dev) if want_kv else None
+    x, p, S = _input_or_slabs(qkv)
+    kernels().rope_kv(x, pos, cos, sin, Hq, Hkv, q, k, v, k_cache, v_cache, slots, p, S, bias, k_scale, v_scale)
     return q, k, v
 
 
@@ -228,17 +227,14 @@ def silu_quantize_fp8(gu, block: int | None = GU_BLOCK) -> tuple[torch.Tensor, t
     the gate|up GEMM's split-K slabs (:class:`SplitK`), summed inside the kernel."""
     M, N2 = gu.shape
     inter = N2 // 2
-    if gu.is_cuda and block == GU_BLOCK and inter <= 16384 and N2 % 128 == 0:
+    slabs = isinstance(gu, SplitK)
+    if (slabs or (gu.is_cuda and gu.stride(1) == 1)) and block == GU_BLOCK and inter <= 16384 and N2 % 128 == 0:
         q = torch.empty(M, inter, dtype=torch.float8_e4m3fn, device=gu.device)
         sx = torch.empty(M, dtype=torch.float32, device=gu.device)
-        if isinstance(gu, SplitK):
-            kernels().silu_quantize_fp8(torch.empty(M, N2, dtype=torch.bfloat16, device=gu.device), q, sx,
-                                        gu.p, gu.S)
-            return q, sx
-        if gu.stride(1) == 1:
-            kernels().silu_quantize_fp8(gu, q, sx)
-            return q, sx
-    if isinstance(gu, SplitK):
+        x, p, S = _input_or_slabs(gu)
+        kernels().silu_quantize_fp8(x, q, sx, p, S)
+        return q, sx
+    if slabs:
         gu = gu.materialize()
     return quantize_fp8(silu_mul(gu, block=block))
 
@@ -333,17 +329,26 @@ def attn_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, b
             out.copy_(r)
             r = out
         return quantize_fp8(r.reshape(r.shape[0], -1)) if quant else r
-    B, Hq, D = q.shape
+    return _attn_decode_launch(q, q.shape, k_cache, v_cache, block_tables, seq_lens, scale, num_splits, out,
+                               workspace, variant, k_scale, v_scale, quant)
+
+
+def _attn_decode_launch(q, shape, k_cache, v_cache, block_tables, seq_lens, scale, num_splits, out, workspace,
+                        variant, k_scale, v_scale, quant, rope=()):
+    """The output / workspace / q8 allocation and the launch of ``attn_decode`` (``q`` rotated) and
+    ``attn_decode_rope`` (``q`` None; ``rope``: the binding's fused-RoPE arguments)."""
+    B, Hq, D = shape
+    dev = k_cache.device
     variant = DECODE_ATTN_VARIANT if variant is None else variant
-    o = out if out is not None else torch.empty_like(q)
+    o = out if out is not None else torch.empty(B, Hq, D, dtype=torch.bfloat16, device=dev)
     if workspace is None:
-        workspace = decode_workspace(B, Hq, num_splits, q.device)
+        workspace = decode_workspace(B, Hq, num_splits, dev)
     q8 = sx = None
     if quant:
-        q8 = torch.empty(B, Hq * D, dtype=torch.float8_e4m3fn, device=q.device)
-        sx = torch.empty(B, dtype=torch.float32, device=q.device)
+        q8 = torch.empty(B, Hq * D, dtype=torch.float8_e4m3fn, device=dev)
+        sx = torch.empty(B, dtype=torch.float32, device=dev)
     kernels().attn_decode(q, k_cache, v_cache, block_tables, seq_lens, o, workspace[0], workspace[1],
-                          num_splits, scale, variant, k_scale, v_scale, q8, sx)
+                          num_splits, scale, variant, k_scale, v_scale, q8, sx, *rope)
     return (q8, sx) if quant else o
 
 
@@ -368,25 +373,15 @@ def attn_decode_rope(qkv, pos: torch.Tensor, cos: torch.Tensor, sin: torch.Tenso
     reading it (csrc/kernels/attn_decode.hip, ``DecRope``). Same numerics as the two
     kernels; one launch and the q round trip fewer per layer."""
     Hkv = k_cache.shape[1]
-    if not (qkv.is_cuda and FUSED_DECODE_ROPE and qkv.shape[0] * Hkv <= FUSED_ROPE_MAX_SEQ_HEADS):
+    on_gpu = isinstance(qkv, SplitK) or qkv.is_cuda
+    if not (on_gpu and FUSED_DECODE_ROPE and qkv.shape[0] * Hkv <= FUSED_ROPE_MAX_SEQ_HEADS):
         q, _, _ = rope_kv(qkv, pos, cos, sin, Hq, Hkv, k_cache, v_cache, slots, want_kv=False, bias=bias,
                           k_scale=k_scale, v_scale=v_scale)
         return attn_decode(q, k_cache, v_cache, block_tables, seq_lens, scale, num_splits, workspace=workspace,
                            variant=variant, k_scale=k_scale, v_scale=v_scale, quant=quant)
-    B = qkv.shape[0]
-    D = cos.shape[1] * 2
-    variant = DECODE_ATTN_VARIANT if variant is None else variant
-    o = torch.empty(B, Hq, D, dtype=torch.bfloat16, device=qkv.device)
-    if workspace is None:
-        workspace = decode_workspace(B, Hq, num_splits, qkv.device)
-    q8 = sx = None
-    if quant:
-        q8 = torch.empty(B, Hq * D, dtype=torch.float8_e4m3fn, device=qkv.device)
-        sx = torch.empty(B, dtype=torch.float32, device=qkv.device)
-    rx, S = (qkv.p, qkv.S) if isinstance(qkv, SplitK) else (qkv, 1)
-    kernels().attn_decode(o, k_cache, v_cache, block_tables, seq_lens, o, workspace[0], workspace[1], num_splits,
-                          scale, variant, k_scale, v_scale, q8, sx, rx, S, pos, cos, sin, slots, bias)
-    return (q8, sx) if quant else o
+    return _attn_decode_launch(None, (qkv.shape[0], Hq, cos.shape[1] * 2), k_cache, v_cache, block_tables, seq_lens,
+                               scale, num_splits, None, workspace, variant, k_scale, v_scale, quant,
+                               rope=(*_input_or_slabs(qkv), pos, cos, sin, slots, bias))
 
 
 def sample_threshold(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor,

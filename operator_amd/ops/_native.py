@@ -55,7 +55,7 @@ def kernels():
     with _lock:
         if _C is not None:
             return _C
-        _check_fresh("_C", ("csrc/kernels/*", "csrc/*.cpp"))
+        _check_fresh("_C", ("csrc/kernels/*", "csrc/*.cpp", "csrc/*.h"))
         try:
             _C = importlib.import_module("operator_amd._C")
         except ImportError as e:  # not built yet

@@ -23,14 +23,15 @@ from ._native import kernels
 
 
 class SplitK:
-    """A decode GEMM's output left as S fp32 split-K slabs [S, M, N]; the consumer
-    (rmsnorm) sums them, so the GEMM's separate reduction pass disappears."""
+    """A GEMM's output left as S fp32 split-K slabs [S, M, N]; the consumer (rmsnorm, rope_kv,
+    silu_quantize_fp8, the fused decode RoPE, the fused all-reduce + norm) sums them in slab order
+    and rounds to bf16 once, so the GEMM's separate reduction pass disappears. Not a tensor: a
+    consumer tests ``isinstance`` first."""
 
-    __slots__ = ("p", "S", "shape", "device", "dtype", "is_cuda")
+    __slots__ = ("p", "S", "shape", "device")
 
     def __init__(self, p: torch.Tensor, S: int, M: int, N: int):
-        self.p, self.S, self.shape = p, S, (M, N)
-        self.device, self.dtype, self.is_cuda = p.device, torch.bfloat16, True
+        self.p, self.S, self.shape, self.device = p, S, (M, N), p.device
 
     def materialize(self) -> torch.Tensor:
         M, N = self.shape

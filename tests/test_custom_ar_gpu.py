@@ -82,7 +82,7 @@ def _worker(rank: int, world: int, port: int, q, protocol: str = "auto") -> None
             assert torch.equal(h, h_ref), (rows, hidden, (h.float() - h_ref.float()).abs().max())
             torch.testing.assert_close(y.float(), y_ref.float(), atol=1e-2, rtol=1e-2)
             # split-K slabs in (summed in slab order, bf16-rounded) and e4m3fn rows out
-            for S in (2, 3, 4):   # two- and four-slab paths load every slab together; 3: the loop
+            for S in (1, 2, 3, 4, 5, 8):   # two- and four-slab paths load every slab together; else the loop
                 ps = [(_inputs(50 + r, S * rows * hidden, torch.float32, call) / S).view(S, rows, hidden)
                       for r in range(world)]
                 ts = []
