@@ -183,7 +183,7 @@ def attn_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, seq_lens: li
         r = reference.attn_prefill(q, k, v, cu, scale,
                                    prefix=None if prefix is None else (prefix[0], prefix[1], prefix[3]))
         if out is not None:
-            out.copy_(r)
+            out[:cu[-1]].copy_(r[:cu[-1]])   # like the kernels: rows past the last sequence are not written
             return out
         return r
     o = out if out is not None else torch.empty_like(q)
