@@ -18,6 +18,12 @@ def _rand(*shape, scale=1.0):
     return (torch.randn(*shape, device=DEV) * scale).to(torch.bfloat16)
 
 
+def _nan(*shape, dtype=torch.bfloat16):
+    """An output or slab buffer that starts as NaN: an element the kernel does not write fails the
+    comparison (a fresh torch.empty hands back the block the previous variant just filled)."""
+    return torch.full(shape, float("nan"), dtype=dtype, device=DEV)
+
+
 def _close(y, r, tol=2e-2):
     torch.testing.assert_close(y.float(), r.float(), atol=tol, rtol=tol)
 
@@ -33,10 +39,10 @@ def test_gemm_tile_store_and_bias(M, N, K):
     r = x.float() @ w.float().t()
     b = _rand(N, scale=0.5)
     for v in VARIANTS:
-        y = torch.empty(M, N, dtype=torch.bfloat16, device=DEV)
+        y = _nan(M, N)
         ops.kernels().gemm_tile(x, w, y, None, False, v)
         _close(y, r)
-        yb = torch.empty_like(y)
+        yb = _nan(M, N)
         ops.kernels().gemm_tile(x, w, yb, b, False, v)
         _close(yb, r + b.float())
 
@@ -52,7 +58,7 @@ def test_gemm_tile_layout_exact():
     w[5, 17] = 1   # column 5 of y = x[:, 17]
     r = x.float() @ w.float().t()     # exact in fp32; y is that rounded once to bf16
     for v in VARIANTS:
-        y = torch.empty(M, N, dtype=torch.bfloat16, device=DEV)
+        y = _nan(M, N)
         ops.kernels().gemm_tile(x, w, y, None, False, v)
         assert torch.equal(y, r.to(torch.bfloat16))
         assert torch.equal(y[:, 5].float(), x[:, 17].float())
@@ -70,7 +76,7 @@ def test_gemm_tile_silu(M, inter, K):
     uu = (x.float() @ u.float().t()).to(torch.bfloat16)
     r = ref.silu_mul(torch.cat([gg, uu], 1), None)
     for v in VARIANTS:
-        y = torch.empty(M, inter, dtype=torch.bfloat16, device=DEV)
+        y = _nan(M, inter)
         ops.kernels().gemm_tile(x, wgu, y, None, True, v)
         _close(y, r, 3e-2)
 
@@ -83,18 +89,18 @@ def test_gemm_tile_split_k(S):
     torch.manual_seed(S)
     x, w = _rand(M, K), _rand(N, K, scale=0.05)
     r = x.float() @ w.float().t()
-    P = torch.empty(S * M * N, dtype=torch.float32, device=DEV)
+    P = _nan(S * M * N, dtype=torch.float32)
     ops.kernels().gemm_tile(x, w, None, None, False, 0, S, P)
     torch.cuda.synchronize()
     _close(P.view(S, M, N).sum(0), r, 1e-3)
-    y = torch.empty(M, N, dtype=torch.bfloat16, device=DEV)
+    y = _nan(M, N)
     ops.kernels().gemm_tile(x, w, y, None, False, 0, S, P)
     _close(y, r)
     g, u = _rand(256, K, scale=0.05), _rand(256, K, scale=0.05)
     wgu = ops.interleave_gate_up(g, u)
     gg = (x.float() @ g.float().t()).to(torch.bfloat16)
     uu = (x.float() @ u.float().t()).to(torch.bfloat16)
-    ys = torch.empty(M, 256, dtype=torch.bfloat16, device=DEV)
+    ys = _nan(M, 256)
     ops.kernels().gemm_tile(x, wgu, ys, None, True, 0, S, P)
     _close(ys, ref.silu_mul(torch.cat([gg, uu], 1), None), 3e-2)
 
@@ -115,7 +121,7 @@ def test_gemm_tile_persistent_rounds(M, N, K, epi):
         gg = (x.float() @ g.float().t()).to(torch.bfloat16)
         uu = (x.float() @ u.float().t()).to(torch.bfloat16)
         r = ref.silu_mul(torch.cat([gg, uu], 1), None)
-        y = torch.empty(M, N // 2, dtype=torch.bfloat16, device=DEV)
+        y = _nan(M, N // 2)
         ops.kernels().gemm_tile(x, w, y, None, True, 5)
         _close(y, r, 3e-2)
         return
@@ -123,7 +129,7 @@ def test_gemm_tile_persistent_rounds(M, N, K, epi):
     b = _rand(N, scale=0.5) if epi == "bias" else None
     r = x.float() @ w.float().t() + (b.float() if b is not None else 0.0)
     for v in ((5, 6, 7, 8, 9, 10, 11, 12, 13, 14) if b is None else (5,)):   # 6-14: p5 schedule arms (store epilogue)
-        y = torch.empty(M, N, dtype=torch.bfloat16, device=DEV)
+        y = _nan(M, N)
         ops.kernels().gemm_tile(x, w, y, b, False, v)
         _close(y, r)
 
@@ -141,7 +147,7 @@ def test_gemm_tile_strided_output():
 def test_gemm_tile_rejects_bad_shapes():
     x, w = _rand(8, 100), _rand(32, 100)
     with pytest.raises(RuntimeError):
-        ops.kernels().gemm_tile(x, w, torch.empty(8, 32, dtype=torch.bfloat16, device=DEV))
+        ops.kernels().gemm_tile(x, w, _nan(8, 32))
 
 
 @pytest.mark.parametrize("M", [1, 64, 130, 256])
@@ -153,13 +159,13 @@ def test_gemm_pp_decode(M, N, K):
     x = _rand(M, K)
     w = _rand(N, K, scale=0.05)
     r = x.float() @ w.float().t()
-    P = torch.empty(8 * M * N, dtype=torch.float32, device=DEV)
+    P = _nan(8 * M * N, dtype=torch.float32)
     for bm in (128, 256):
         for S in (1, 2, 4, 8):
             if K % (64 * S):
                 continue
             for nt in (True, False):
-                y = torch.empty(M, N, dtype=torch.bfloat16, device=DEV)
+                y = _nan(M, N)
                 ops.kernels().gemm_pp(x, w, y, P if S > 1 else None, S, bm, False, nt)
                 _close(y, r)
             if S > 1:
@@ -167,7 +173,7 @@ def test_gemm_pp_decode(M, N, K):
                 torch.cuda.synchronize()
                 _close(P[:S * M * N].view(S, M, N).sum(0), r)
             if bm == 256:   # one barrier segment per K-tile
-                y = torch.empty(M, N, dtype=torch.bfloat16, device=DEV)
+                y = _nan(M, N)
                 ops.kernels().gemm_pp(x, w, y, P if S > 1 else None, S, bm, False, True, True)
                 _close(y, r)
 
@@ -184,6 +190,6 @@ def test_gemm_pp_silu(M):
     uu = (x.float() @ u.float().t()).to(torch.bfloat16)
     r = ref.silu_mul(torch.cat([gg, uu], 1), None)
     for bm, one in ((128, False), (256, False), (256, True)):
-        y = torch.empty(M, inter, dtype=torch.bfloat16, device=DEV)
+        y = _nan(M, inter)
         ops.kernels().gemm_pp(x, wgu, y, None, 1, bm, True, True, one)
         _close(y, r, 3e-2)

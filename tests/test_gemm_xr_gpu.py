@@ -17,6 +17,11 @@ def _rand(*shape, scale=1.0):
     return (torch.randn(*shape, device=DEV) * scale).to(torch.bfloat16)
 
 
+def _nan(*shape, dtype=torch.bfloat16):
+    """A GEMM output or slab buffer that starts as NaN: an element the kernel does not write fails."""
+    return torch.full(shape, float("nan"), dtype=dtype, device=DEV)
+
+
 def untile(xt: torch.Tensor, M: int, K: int) -> torch.Tensor:
     """The tiled layout [K/64][M/16][2 k-half][4 (k%32)/8][16 row%16][8] -> row-major [M, K]."""
     return xt.reshape(K // 64, M // 16, 2, 4, 16, 8).permute(1, 4, 0, 2, 3, 5).reshape(M, K)
@@ -40,12 +45,12 @@ def test_gemm_xr_slabs_and_store(N, K, S):
     r = x.float() @ w.float().t()
     xt = torch.empty_like(x)
     ops.kernels().tile_rows(x, xt)
-    P = torch.empty(S * 256 * N, dtype=torch.float32, device=DEV)
+    P = _nan(S * 256 * N, dtype=torch.float32)
     ops.kernels().gemm_xr(xt, w, None, P, S, 0)
     torch.cuda.synchronize()
     torch.testing.assert_close(P.view(S, 256, N).sum(0), r, atol=2e-3, rtol=2e-3)
     if S == 1:
-        y = torch.empty(256, N, dtype=torch.bfloat16, device=DEV)
+        y = _nan(256, N)
         ops.kernels().gemm_xr(xt, w, y, None, 1, 1)
         torch.testing.assert_close(y.float(), r, atol=2e-2, rtol=2e-2)
 
@@ -61,11 +66,11 @@ def test_gemm_xr_swiglu_rows_and_tiled(inter, K):
     r = ref.silu_mul(torch.cat([gg, uu], 1), None)
     xt = torch.empty_like(x)
     ops.kernels().tile_rows(x, xt)
-    y = torch.empty(256, inter, dtype=torch.bfloat16, device=DEV)
+    y = _nan(256, inter)
     ops.kernels().gemm_xr(xt, wgu, y, None, 1, 2)
     torch.testing.assert_close(y.float(), r.float(), atol=3e-2, rtol=3e-2)
     if inter % 64 == 0:
-        yt = torch.empty(256, inter, dtype=torch.bfloat16, device=DEV)
+        yt = _nan(256, inter)
         ops.kernels().gemm_xr(xt, wgu, yt, None, 1, 3)
         torch.cuda.synchronize()
         assert torch.equal(untile(yt, 256, inter), y)   # same values, tiled for the next gemm_xr
@@ -96,7 +101,7 @@ def test_rmsnorm_tiled_output_feeds_gemm_xr():
     torch.cuda.synchronize()
     assert torch.equal(r3, r4) and torch.equal(untile(yst, M, H), ys)
     w = _rand(1024, H, scale=0.05)
-    P2 = torch.empty(4 * M * 1024, dtype=torch.float32, device=DEV)
+    P2 = _nan(4 * M * 1024, dtype=torch.float32)
     ops.kernels().gemm_xr(yst, w, None, P2, 4, 0)
     torch.cuda.synchronize()
     torch.testing.assert_close(P2.view(4, M, 1024).sum(0), ys.float() @ w.float().t(), atol=2e-3, rtol=2e-3)

@@ -15,6 +15,12 @@ def _rand(*shape, dtype=torch.bfloat16, scale=1.0):
     return (torch.randn(*shape, device=DEV) * scale).to(dtype)
 
 
+def _nan(*shape, dtype=torch.bfloat16):
+    """A GEMM output or slab buffer that starts as NaN: an element the kernel does not write fails
+    the comparison (a fresh torch.empty hands back the block the previous launch just filled)."""
+    return torch.full(shape, float("nan"), dtype=dtype, device=DEV)
+
+
 def test_native_module_is_loaded():
     C = ops.kernels()
     assert C.ARCH == "gfx950"
@@ -193,11 +199,13 @@ def test_gemm_decode(M, N, K):
                 if M % bm or K // 64 < S or N % bn:
                     continue
                 for ns in ((2, 3, 4) if bm <= 128 else (3, 4) if bm + bn <= 320 else (3,)):
-                    y = ops.linear(x, w, splits=S, bn=bn, bm=bm, stages=ns)
+                    y = ops.linear(x, w, out=_nan(M, N), splits=S, bn=bn, bm=bm, stages=ns,
+                                   partial=_nan(S * M * N, dtype=torch.float32) if S > 1 else None)
                     torch.testing.assert_close(y.float(), ref_, atol=2e-2, rtol=2e-2)
     # default split choice and the hipBLASLt fallback shape agree too
-    torch.testing.assert_close(ops.linear(x, w).float(), ref_, atol=2e-2, rtol=2e-2)
-    torch.testing.assert_close(ops.linear(x[:M - 3].contiguous(), w).float(), ref_[:M - 3], atol=2e-2, rtol=2e-2)
+    torch.testing.assert_close(ops.linear(x, w, out=_nan(M, N)).float(), ref_, atol=2e-2, rtol=2e-2)
+    torch.testing.assert_close(ops.linear(x[:M - 3].contiguous(), w, out=_nan(M - 3, N)).float(), ref_[:M - 3],
+                               atol=2e-2, rtol=2e-2)
 
 
 @pytest.mark.parametrize("M", [1, 2, 5, 16, 17, 32])
@@ -214,15 +222,15 @@ def test_gemm_skinny(M, N, K):
     for S in (1, 2, 4, 8):
         if K % (128 * S):
             continue
-        y = torch.empty(M, N, dtype=torch.bfloat16, device=DEV)
-        p = torch.empty(S * M * N, dtype=torch.float32, device=DEV) if S > 1 else None
+        y = _nan(M, N)
+        p = _nan(S * M * N, dtype=torch.float32) if S > 1 else None
         kernels().gemm_skinny(x, w, y, p, S, False)
         torch.testing.assert_close(y.float(), ref_, atol=2e-2, rtol=2e-2)
         if S > 1:
             torch.testing.assert_close(p.view(S, M, N).sum(0), ref_, atol=1e-3, rtol=1e-3)
-            d = ops.linear(x, w, splits=S, defer_reduce=True)
+            d = ops.linear(x, w, splits=S, defer_reduce=True, partial=_nan(S * M * N, dtype=torch.float32))
             torch.testing.assert_close(d.materialize().float(), ref_, atol=2e-2, rtol=2e-2)
-    torch.testing.assert_close(ops.linear(x, w).float(), ref_, atol=2e-2, rtol=2e-2)
+    torch.testing.assert_close(ops.linear(x, w, out=_nan(M, N)).float(), ref_, atol=2e-2, rtol=2e-2)
 
 
 @pytest.mark.parametrize("M", [64, 128, 192, 256, 40, 1, 7, 16, 32])
@@ -245,7 +253,7 @@ def test_gate_up_silu_fused(M):
             for ns in (2, 3, 4):
                 if bm > M or M % bm or (ns == 2 and bm != 64) or (ns == 4 and bm == 256):
                     continue
-                y = torch.empty(M, inter, dtype=x.dtype, device=x.device)
+                y = _nan(M, inter)
                 ops.kernels().gemm_decode(x, wgu, y, None, 1, 128, bm, True, False, ns)
                 torch.testing.assert_close(y.float(), ref_.float(), atol=2e-2, rtol=2e-2, msg=f"bm={bm} ns={ns}")
 
@@ -274,7 +282,7 @@ def test_gate_up_silu_stream_k(M, inter, K):
         torch.cuda.synchronize()
         torch.testing.assert_close(y.float(), ref_, atol=2e-2, rtol=2e-2)
         assert int(fl.abs().sum()) == 0
-    y0 = torch.empty(M, inter, dtype=torch.bfloat16, device=DEV)
+    y0 = _nan(M, inter)
     kernels().gemm_pp(x, wgu, y0, None, 1, 256, True, True)
     torch.testing.assert_close(y0.float(), ref_, atol=2e-2, rtol=2e-2)
     # the sums differ only in fp32 association (the cut tile's partial is added last): the bf16
@@ -356,11 +364,11 @@ def test_gemm_fp8(M, N, K):
             for S in (1, 2, 3, 4, 8, 12):   # 3 / 12: uneven K slices
                 if K // 128 < S or N % bn:
                     continue
-                y = ops.linear_fp8(x, w8, sw, plan=(bm, bn, S))
+                y = ops.linear_fp8(x, w8, sw, out=_nan(M, N), plan=(bm, bn, S))
                 torch.testing.assert_close(y.float(), ref_, atol=2e-2, rtol=2e-2)
     # and W8A8 stays close to the bf16 product (e4m3: ~3 mantissa bits per operand)
     exact = x.float() @ w.float().t()
-    rel = (ops.linear_fp8(x, w8, sw).float() - exact).norm() / exact.norm()
+    rel = (ops.linear_fp8(x, w8, sw, out=_nan(M, N)).float() - exact).norm() / exact.norm()
     assert rel < 0.06, float(rel)
 
 
