@@ -593,6 +593,66 @@ void sample(const at::Tensor& logits, const at::Tensor& temperature, const at::T
                          ptr<int64_t>(out), col_offset, optr<float>(out_val), cur_stream(), optr<float>(thr)));
 }
 
+// The penalty table (kernels.h PenaltyTable) from its three int32 tensors: cnt [slots, vocab],
+// lst [slots, cap], n [slots], contiguous on `dev`.
+static oamd::PenaltyTable penalty_table(const at::Tensor& cnt, const at::Tensor& lst, const at::Tensor& n,
+                                        const at::Device& dev) {
+  for (const at::Tensor* t : {&cnt, &lst, &n}) {
+    CHECK_DEV(*t); CHECK_DT(*t, at::kInt); CHECK_CONTIG(*t);
+    TORCH_CHECK(t->device() == dev, "the penalty table must be on the device of the other operands");
+  }
+  TORCH_CHECK(cnt.dim() == 2 && lst.dim() == 2 && n.dim() == 1, "penalty table: cnt [slots, vocab], lst [slots, cap], n [slots]");
+  TORCH_CHECK(lst.size(0) == cnt.size(0) && n.size(0) == cnt.size(0), "penalty table: cnt, lst and n differ in slots");
+  TORCH_CHECK(cnt.size(0) < (1 << 30) && cnt.size(1) < (int64_t(1) << 31) && lst.size(1) < (int64_t(1) << 31),
+              "penalty table too large");
+  return {ptr<int>(cnt), ptr<int>(lst), ptr<int>(n), (int)cnt.size(0), (int)cnt.size(1), (int)lst.size(1)};
+}
+
+// Clear the slots named and flag their requests' whole prompts (kernels.h penalty_seed): slots int32 [R],
+// ids int64 [N] packed prompts, cu int32 [R + 1] offsets into ids.
+void penalty_seed(const at::Tensor& slots, const at::Tensor& ids, const at::Tensor& cu, at::Tensor& cnt,
+                  at::Tensor& lst, at::Tensor& n) {
+  for (const at::Tensor* t : {&slots, &ids, &cu}) { CHECK_DEV(*t); CHECK_CONTIG(*t); }
+  CHECK_DT(slots, at::kInt); CHECK_DT(ids, at::kLong); CHECK_DT(cu, at::kInt);
+  TORCH_CHECK(slots.dim() == 1 && ids.dim() == 1 && cu.dim() == 1 && cu.numel() == slots.numel() + 1,
+              "penalty_seed: slots [R], ids [N], cu [R + 1]");
+  TORCH_CHECK(ids.device() == slots.device() && cu.device() == slots.device(), "penalty_seed: operands on one device");
+  const oamd::PenaltyTable tb = penalty_table(cnt, lst, n, slots.device());
+  const c10::hip::HIPGuardMasqueradingAsCUDA g(slots.device());
+  RC(oamd::penalty_seed(ptr<int>(slots), (int)slots.numel(), ptr<int64_t>(ids), ids.numel(), ptr<int>(cu), tb,
+                        cur_stream()));
+}
+
+// Count last_tok (optional) and apply the penalties to the logits in place (kernels.h sample_penalty).
+void sample_penalty(at::Tensor& logits, const at::Tensor& pslot, const c10::optional<at::Tensor>& last_tok,
+                    const c10::optional<at::Tensor>& ctx, const at::Tensor& rep, const at::Tensor& freq,
+                    const at::Tensor& pres, at::Tensor& cnt, at::Tensor& lst, at::Tensor& n) {
+  CHECK_DEV(logits);
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && logits.stride(0) >= logits.size(1),
+              "logits must be [rows, vocab] row-major");
+  TORCH_CHECK(logits.scalar_type() == at::kBFloat16 || logits.scalar_type() == at::kFloat, "logits dtype");
+  const int64_t rows = logits.size(0);
+  for (const at::Tensor* t : {&pslot, &rep, &freq, &pres}) {
+    CHECK_DEV(*t); CHECK_CONTIG(*t);
+    TORCH_CHECK(t->numel() == rows && t->device() == logits.device(), "penalty per-row tensor shape / device");
+  }
+  CHECK_DT(pslot, at::kInt); CHECK_DT(rep, at::kFloat); CHECK_DT(freq, at::kFloat); CHECK_DT(pres, at::kFloat);
+  if (last_tok.has_value()) {
+    CHECK_DEV(*last_tok); CHECK_DT(*last_tok, at::kLong); CHECK_CONTIG(*last_tok);
+    TORCH_CHECK(last_tok->numel() == rows && last_tok->device() == logits.device(), "last_tok shape / device");
+  }
+  if (ctx.has_value()) {
+    CHECK_DEV(*ctx); CHECK_DT(*ctx, at::kInt); CHECK_CONTIG(*ctx);
+    TORCH_CHECK(ctx->numel() == rows && ctx->device() == logits.device(), "ctx shape / device");
+  }
+  const oamd::PenaltyTable tb = penalty_table(cnt, lst, n, logits.device());
+  TORCH_CHECK(logits.size(1) <= tb.vocab, "logits have more columns than the penalty table");
+  const c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
+  RC(oamd::sample_penalty(logits.data_ptr(), logits.scalar_type() == at::kBFloat16, logits.stride(0), (int)rows,
+                          (int)logits.size(1), ptr<int>(pslot), optr<int64_t>(last_tok), optr<int>(ctx), ptr<float>(rep),
+                          ptr<float>(freq), ptr<float>(pres), tb, cur_stream()));
+}
+
 // thr[row] = the top-k / top-p threshold of each row (kernels.h sample_threshold); kept: optional counts.
 void sample_threshold(const at::Tensor& logits, const at::Tensor& temperature, const at::Tensor& top_k,
                       const at::Tensor& top_p, at::Tensor& thr, const c10::optional<at::Tensor>& kept) {
@@ -691,6 +751,11 @@ PYBIND11_MODULE(_C, m) {
         pybind11::arg("out_val") = pybind11::none(), pybind11::arg("thr") = pybind11::none());
   m.def("sample_threshold", &sample_threshold, pybind11::arg("logits"), pybind11::arg("temperature"),
         pybind11::arg("top_k"), pybind11::arg("top_p"), pybind11::arg("thr"), pybind11::arg("kept") = pybind11::none());
+  m.def("penalty_seed", &penalty_seed, pybind11::arg("slots"), pybind11::arg("ids"), pybind11::arg("cu"),
+        pybind11::arg("cnt"), pybind11::arg("lst"), pybind11::arg("n"));
+  m.def("sample_penalty", &sample_penalty, pybind11::arg("logits"), pybind11::arg("pslot"), pybind11::arg("last_tok"),
+        pybind11::arg("ctx"), pybind11::arg("rep"), pybind11::arg("freq"), pybind11::arg("pres"), pybind11::arg("cnt"),
+        pybind11::arg("lst"), pybind11::arg("n"));
   m.def("graph_launch", &graph_launch, pybind11::arg("graph_exec"), pybind11::arg("count"), pybind11::arg("stream"));
   register_scan_bindings(m);
   register_comm_bindings(m);

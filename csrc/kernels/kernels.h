@@ -143,6 +143,26 @@ int sample_threshold(const void* logits, bool logits_bf16, int64_t stride, int r
                      const float* temperature, const int* top_k, const float* top_p, float* thr, int* kept,
                      hipStream_t stream);
 
+// Repetition / frequency / presence penalties (penalty.hip). One slot of the table per penalised
+// request: cnt [slots][vocab] (bit 31: the token is in the prompt; bits 0-30: times generated),
+// lst [slots][cap] (the distinct tokens whose cnt word is non-zero, any order), n [slots].
+struct PenaltyTable {
+  int* cnt;
+  int* lst;
+  int* n;
+  int slots, vocab, cap;
+};
+// Clear slot slots[b] (walking its list) and flag the tokens ids[cu[b] .. cu[b + 1]) of request b's
+// whole prompt; ids >= vocab and slots < 0 are ignored. One workgroup per request, distinct slots.
+int penalty_seed(const int* slots, int reqs, const int64_t* ids, int64_t total, const int* cu, PenaltyTable table,
+                 hipStream_t stream);
+// In place, per row with pslot[row] >= 0 (and ctx[row] != 0 when ctx is given): count last_tok[row]
+// (when given) in the row's slot, then for every seen token y = x; seen and rep != 1: y > 0 ? y / rep :
+// y * rep; generated c > 0 times: y -= freq * c + pres; each fp32 operation rounded on its own.
+int sample_penalty(void* logits, bool logits_bf16, int64_t stride, int rows, int vocab, const int* pslot,
+                   const int64_t* last_tok, const int* ctx, const float* rep, const float* freq, const float* pres,
+                   PenaltyTable table, hipStream_t stream);
+
 // One-shot all-reduce over peer-mapped fine-grained buffers (allreduce.hip).
 size_t car_buffer_bytes(size_t cap_bytes, int world);
 int car_alloc(size_t cap_bytes, int world, void** base, void* handle_out /* 64 B hipIpcMemHandle_t */);

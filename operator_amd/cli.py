@@ -84,6 +84,9 @@ def cmd_explain(args) -> int:
         extra["top_k"] = str(args.top_k)
     if args.top_p is not None and args.top_p != 1.0:
         extra["top_p"] = str(args.top_p)
+    for name, off in (("repetition_penalty", 1.0), ("frequency_penalty", 0.0), ("presence_penalty", 0.0)):
+        if getattr(args, name) != off:
+            extra[name] = str(getattr(args, name))
     cfg = AIProviderConfig(max_tokens=args.max_tokens, temperature=args.temperature, additional_headers=extra or None)
     outs = ee.explain_many([(r, cfg) for r in res])
     print(json.dumps([o.to_obj() if hasattr(o, "to_obj") else {"error": str(o)} for o in outs], indent=1))
@@ -363,6 +366,13 @@ def main(argv: list[str] | None = None) -> int:
     p.add_argument("--top-k", type=int, default=0, help="sample among the k most likely tokens (0 = off)")
     p.add_argument("--top-p", type=float, default=1.0,
                    help="nucleus sampling: the smallest set of tokens holding this probability (1 = off)")
+    p.add_argument("--repetition-penalty", type=float, default=1.0,
+                   help="divide (multiply, if negative) the logit of every token of the prompt or the output "
+                        "so far by this (1 = off)")
+    p.add_argument("--frequency-penalty", type=float, default=0.0,
+                   help="subtract this times the number of times a token was generated from its logit (0 = off)")
+    p.add_argument("--presence-penalty", type=float, default=0.0,
+                   help="subtract this from the logit of every token generated so far (0 = off)")
     p = sub.add_parser("serve-compat")
     common(p)
     p.add_argument("--patterns", action="append")

@@ -142,6 +142,10 @@ class EngineCfg(BaseModel):
     prefix_sharing: bool = True       # prompts starting with the same whole KV pages share them (computed once)
     warmup_graphs: bool = True        # engine processes capture their graphs before reporting ready
     multi_step: int = 8
+    # slots of the penalty table (repetition / frequency / presence penalties; one per penalised
+    # request in flight, 4 x vocab bytes each): None = max_batch, 0 = no table, no penalty kernel in
+    # the graphs, and requests that set a penalty are refused
+    penalty_slots: int | None = None
     ignore_eos: bool = False
 
 

@@ -13,7 +13,9 @@ caching on / 500 tokens / T=0.3 per AIInterfaceClient.java:78-84):
 * ``cachingEnabled`` -> LRU of responses keyed by (model, prompt, T, maxTokens)
 * ``additionalConfig`` -> ``top_k`` / ``top_p`` (string values, "Provider specific settings";
                         the CRD has no field of its own for them): top-k / nucleus sampling
-                        of the on-node engine, part of the cache key when set
+                        of the on-node engine, part of the cache key when set;
+                        ``repetition_penalty`` / ``frequency_penalty`` / ``presence_penalty``
+                        (string values too): penalties on tokens already seen, likewise
 * ``promptTemplate`` -> operator_amd.engine.prompt.render
 
 Requests from any number of threads are batched continuously by one engine
@@ -22,6 +24,7 @@ loop thread that owns the GPU (LLMEngine.step).
 from __future__ import annotations
 
 import hashlib
+import math
 import sys
 import threading
 import time
@@ -275,12 +278,34 @@ class ExplainEngine:
                                f"top_k={top_k}, top_p={top_p}")
         return top_k, top_p
 
+    @staticmethod
+    def _penalties(cfg: AIProviderConfig) -> tuple[float, float, float]:
+        """(repetition_penalty, frequency_penalty, presence_penalty) of an AIProvider's
+        ``additionalConfig`` (string values; absent = off: 1, 0, 0)."""
+        extra = cfg.additional_headers or {}
+        out = []
+        for name, off in (("repetition_penalty", 1.0), ("frequency_penalty", 0.0), ("presence_penalty", 0.0)):
+            v = off
+            if extra.get(name) is not None:
+                try:
+                    v = float(str(extra[name]).strip())
+                except ValueError:
+                    raise ExplainError(f"additionalConfig {name}: not a number ({extra[name]!r})") from None
+                if not math.isfinite(v) or (name == "repetition_penalty" and not v > 0):
+                    raise ExplainError(f"additionalConfig: {name} must be a finite number"
+                                       f"{' > 0' if name == 'repetition_penalty' else ''}, got {v}")
+            out.append(v)
+        return tuple(out)
+
     def _key(self, ids: list[int], cfg: AIProviderConfig) -> str:
         h = hashlib.sha256()
         h.update(f"{cfg.model_id}|{cfg.temperature}|{cfg.max_tokens}|".encode())
         top_k, top_p = self._filters(cfg)
         if top_k > 0 or top_p < 1:   # only when set: the keys of every other provider stay as they were
             h.update(f"top_k={top_k}|top_p={top_p}|".encode())
+        rep, freq, pres = self._penalties(cfg)
+        if rep != 1 or freq != 0 or pres != 0:   # likewise
+            h.update(f"repetition_penalty={rep}|frequency_penalty={freq}|presence_penalty={pres}|".encode())
         h.update(bytes(str(ids), "ascii"))
         return h.hexdigest()
 
@@ -315,8 +340,10 @@ class ExplainEngine:
     def _start(self, p: _Pending, ids: list[int], notify: bool = True) -> None:
         cfg = p.cfg
         top_k, top_p = self._filters(cfg)
+        rep, freq, pres = self._penalties(cfg)
         p.req = GenRequest(ids, max_tokens=max(1, int(cfg.max_tokens)), temperature=float(cfg.temperature),
-                           seed=self._seed(ids) + p.attempt, ignore_eos=self.ignore_eos, top_k=top_k, top_p=top_p)
+                           seed=self._seed(ids) + p.attempt, ignore_eos=self.ignore_eos, top_k=top_k, top_p=top_p,
+                           repetition_penalty=rep, frequency_penalty=freq, presence_penalty=pres)
         self.llm.submit(p.req)
         if notify:
             self.loop.notify()
@@ -412,14 +439,19 @@ class ExplainEngine:
 
     # ------------------------------------------------------------------ raw completions
     def complete(self, ids: list[int], max_tokens: int = 500, temperature: float = 0.3, seed: int | None = None,
-                 timeout_s: float | None = None, top_k: int = 0, top_p: float = 1.0) -> dict:
+                 timeout_s: float | None = None, top_k: int = 0, top_p: float = 1.0,
+                 repetition_penalty: float = 1.0, frequency_penalty: float = 0.0,
+                 presence_penalty: float = 0.0) -> dict:
         """Generate from raw prompt token ids on the same continuous batch as the
         explanations (the OpenAI / Ollama endpoints of engine/server.py). ``top_k`` (0 = off) /
-        ``top_p`` (1 = off): top-k / nucleus sampling. Raises ExplainError on a timeout, an
+        ``top_p`` (1 = off): top-k / nucleus sampling. ``repetition_penalty`` (1 = off) /
+        ``frequency_penalty`` / ``presence_penalty`` (0 = off): penalties on tokens already seen
+        (docs/PARITY.md "Sampling: penalties"). Raises ExplainError on a timeout, an
         engine error, a prompt the engine cannot hold or sampling parameters it rejects."""
         req = GenRequest(list(ids), max_tokens=max(1, int(max_tokens)), temperature=max(0.0, float(temperature)),
                          seed=self._seed(ids) if seed is None else int(seed), ignore_eos=self.ignore_eos,
-                         top_k=top_k, top_p=top_p)
+                         top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
+                         frequency_penalty=frequency_penalty, presence_penalty=presence_penalty)
         want = req.max_tokens
         t0 = time.perf_counter()
         try:

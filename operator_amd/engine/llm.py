@@ -19,12 +19,18 @@ hipGraph-captured decode steps.
   (every explanation prompt starts with the same instructions) map ONE set of pages,
   computed once, at the head of their block tables; their prefill computes only their
   own tokens, attending to the cached prefix K/V (``_SharedPrefix``).
+* Repetition / frequency / presence penalties: a request that sets one owns a slot of the
+  engine's device table of seen tokens (``models/penalty.py``) from admission to reaping. The
+  slot is seeded with the whole prompt ahead of the prefill; every decode step counts the
+  token it feeds in and penalises the logits inside the graph, between lm_head and sampler
+  (``ops.sample_penalty``). Rows of requests without a penalty carry slot -1.
 """
 from __future__ import annotations
 
 import contextlib
 import gc
 import itertools
+import math
 import threading
 import time
 from collections import deque
@@ -36,6 +42,7 @@ import torch
 from operator_amd import ops
 from operator_amd.models.kv_cache import PagedKVCache
 from operator_amd.models.llama import ForwardBatch, LlamaModel
+from operator_amd.models.penalty import PenaltyTable
 from operator_amd.utils.tracing import trace_range
 
 
@@ -55,10 +62,15 @@ class GenRequest:
     ignore_eos: bool = False
     top_k: int = 0          # sample among the k most likely tokens (0 = off)
     top_p: float = 1.0      # ... among the smallest set of them holding this much probability (1 = off)
+    # penalties on tokens already seen (docs/PARITY.md "Sampling: penalties")
+    repetition_penalty: float = 1.0   # seen in the prompt or generated: logit / r if > 0 else * r (1 = off)
+    frequency_penalty: float = 0.0    # generated c > 0 times: logit - f * c (0 = off)
+    presence_penalty: float = 0.0     # ... and - p (0 = off)
     rid: int = -1
     # runtime state
     pages: list[int] = field(default_factory=list)
     prefix: "_SharedPrefix | None" = None   # shared prompt-prefix pages at the head of ``pages``
+    pslot: int = -1                # penalty-table slot from admission to reaping (-1: no penalty set)
     output: list[int] = field(default_factory=list)
     done: bool = False
     cancelled: bool = False
@@ -75,6 +87,10 @@ class GenRequest:
     @property
     def length(self) -> int:
         return len(self.prompt) + len(self.output)
+
+    @property
+    def penalised(self) -> bool:
+        return self.repetition_penalty != 1.0 or self.frequency_penalty != 0.0 or self.presence_penalty != 0.0
 
 
 @dataclass
@@ -168,11 +184,16 @@ class _BucketState:
         mp = eng.max_pages
         self._spec = (("step", (1,), torch.long), ("ids", (bp,), torch.long), ("pos", (bp,), torch.long),
                       ("seeds", (bp,), torch.long), ("ctx", (bp,), torch.int32), ("temp", (bp,), torch.float32),
-                      ("topk", (bp,), torch.int32), ("topp", (bp,), torch.float32), ("bt", (bp, mp), torch.int32))
+                      ("topk", (bp,), torch.int32), ("topp", (bp,), torch.float32),
+                      # penalty-table slot (-1: none) and the three penalties of each row
+                      ("pslot", (bp,), torch.int32), ("rep", (bp,), torch.float32), ("freq", (bp,), torch.float32),
+                      ("pres", (bp,), torch.float32), ("bt", (bp, mp), torch.int32))
         self._nbytes = sum(int(np.prod(s)) * torch.empty((), dtype=dt).element_size() for _, s, dt in self._spec)
         self._buf = torch.zeros(self._nbytes, dtype=torch.uint8, device=dev)
         for n, t in self._views(self._buf).items():
             setattr(self, n, t)
+        self.pslot.fill_(-1)   # no row owns a penalty slot before the first load
+        self.rep.fill_(1.0)
         self.hist = torch.zeros(bp, eng.multi_step, dtype=torch.long, device=dev)
         # steps replayed since the last load: the device counter (``step``, bumped by every
         # replay; hist column = step % multi_step) mirrored on the host, so a window needs
@@ -201,7 +222,13 @@ class _BucketState:
         ids, pos, ctx, bt, temp, seeds = v["ids"], v["pos"], v["ctx"], v["bt"], v["temp"], v["seeds"]
         assert bt.shape[1] == max_pages
         v["topp"][:] = 1.0   # padding rows: unfiltered (topk 0)
+        v["pslot"][:] = -1   # ... and unpenalised (freq / pres 0)
+        v["rep"][:] = 1.0
         if n:
+            v["pslot"][:n] = np.fromiter((r.pslot for r in reqs), dtype=np.int32, count=n)
+            v["rep"][:n] = np.fromiter((r.repetition_penalty for r in reqs), dtype=np.float32, count=n)
+            v["freq"][:n] = np.fromiter((r.frequency_penalty for r in reqs), dtype=np.float32, count=n)
+            v["pres"][:n] = np.fromiter((r.presence_penalty for r in reqs), dtype=np.float32, count=n)
             lens = np.fromiter((r.length for r in reqs), dtype=np.int64, count=n)
             ids[:n] = np.fromiter((r.output[-1] for r in reqs), dtype=np.int64, count=n)
             pos[:n] = lens - 1
@@ -258,6 +285,11 @@ class _DecodeGraph:
         fb = ForwardBatch(st.ids, st.pos, slots, False, None, block_tables=st.bt, context_lens=st.ctx,
                           num_splits=self.splits)
         logits = e.model.forward(fb, e.kv)
+        if e.penalties is not None:
+            # st.ids is the last sampled token of each row, not yet counted: the kernel counts it
+            # in the row's slot, then penalises the seen tokens' logits. Rows without a slot
+            # (pslot -1) and padding rows (ctx 0) leave it at once.
+            ops.sample_penalty(logits, st.pslot, st.ids, st.ctx, st.rep, st.freq, st.pres, e.penalties)
         # threshold kernel + filtered sampler in every graph: rows at the defaults (top_k 0,
         # top_p 1) leave the first at once with thr = -inf and sample as before
         tok = e.model.sample(logits, st.temp, st.seeds, spos, top_k=st.topk, top_p=st.topp, thr=st.thr)
@@ -274,11 +306,14 @@ class _DecodeGraph:
         # warm up on a side stream (allocator + hipBLASLt heuristics), then capture; the
         # state is snapshotted and restored so capture never perturbs live rows
         st = self.st
-        snap = [t.clone() for t in (st.ids, st.pos, st.ctx, st.step)]
+        live = (st.ids, st.pos, st.ctx, st.step, st.pslot)
+        snap = [t.clone() for t in live]
         s = torch.cuda.Stream(device=self.eng.device)
         s.wait_stream(torch.cuda.current_stream())
         saved_ctx = st.ctx.clone()
         st.ctx.zero_()  # all rows padding while warming up: no KV writes
+        st.pslot.fill_(-1)   # ... and no row with a penalty slot: the table is never touched
+        s.wait_stream(torch.cuda.current_stream())   # the two fills above come before the warm-up runs
         with torch.cuda.stream(s):
             for _ in range(2):
                 st.step.zero_()
@@ -289,7 +324,7 @@ class _DecodeGraph:
         with _no_gc(), torch.cuda.graph(g, pool=pool):
             self._run()
         self.graph = g
-        for t, v in zip((st.ids, st.pos, st.ctx, st.step), snap):
+        for t, v in zip(live, snap):
             t.copy_(v)
 
     def run(self, use_graph: bool) -> None:
@@ -323,7 +358,8 @@ class _PrefillGraph:
         # profiles/bench_r4_flagship_idle.jsonl "copyBuffer -> copyBuffer")
         spec = (("ids", T, i64), ("pos", T, i64), ("slots", T, i64), ("last", S, i64), ("seeds", S, i64),
                 ("spos", S, i64), ("cu", S + 1, i32), ("ws", self.W, i32), ("wq", self.W, i32),
-                ("temp", S, torch.float32), ("pfx", S, i32), ("topk", S, i32), ("topp", S, torch.float32))
+                ("temp", S, torch.float32), ("pfx", S, i32), ("topk", S, i32), ("topp", S, torch.float32),
+                ("pslot", S, i32), ("rep", S, torch.float32), ("freq", S, torch.float32), ("pres", S, torch.float32))
         self._layout, off = [], 0
         for n, k, dt in spec:
             isz = torch.empty((), dtype=dt).element_size()
@@ -358,13 +394,17 @@ class _PrefillGraph:
         fb = ForwardBatch(d["ids"], d["pos"], d["slots"], True, d["last"], seq_lens=[],
                           prefill_work=(d["cu"], d["ws"], d["wq"], self.variant), prefix=pre)
         logits = e.model.forward(fb, e.kv)
+        if e.penalties is not None:   # the first token sees the prompt only (seeded before the launch): nothing to count
+            ops.sample_penalty(logits, d["pslot"], None, None, d["rep"], d["freq"], d["pres"], e.penalties)
         self.tok = e.model.sample(logits, d["temp"], d["seeds"], d["spos"], top_k=d["topk"], top_p=d["topp"],
                                   thr=self.thr)
 
     def capture(self, pool) -> None:
-        # every work item padding and every slot -1 while warming up: no KV writes
+        # every work item padding and every slot -1 while warming up: no KV writes, and no
+        # penalty slot on any row: the table is never touched
         self.dev["slots"].fill_(-1)
         self.dev["ws"].fill_(-1)
+        self.dev["pslot"].fill_(-1)
         s = torch.cuda.Stream(device=self.eng.device)
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -376,7 +416,8 @@ class _PrefillGraph:
             self._run()
         self.graph = g
 
-    def launch(self, ids, pos, slots, cu, ws, wq, last, temp, seeds, spos, pfx=None, topk=None, topp=None):
+    def launch(self, ids, pos, slots, cu, ws, wq, last, temp, seeds, spos, pfx=None, topk=None, topp=None,
+               pen=None):
         """Queue one replay for the real batch (numpy inputs, <= T tokens, <= S
         sequences); returns (pinned token buffer, event): ``event`` completes when the
         batch's sampled first tokens are in the buffer."""
@@ -386,7 +427,9 @@ class _PrefillGraph:
             self.events[i].synchronize()   # this set's copies (two launches ago) are done
         h = self.hosts[i]
         b = len(last)
-        for name, arr, fill in (("ids", ids, 0), ("pos", pos, 0), ("slots", slots, -1), ("last", last, 0),
+        pslot, rep, freq, pres = pen if pen is not None else ([], [], [], [])   # (slots, r, f, p) per sequence
+        for name, arr, fill in (("pslot", pslot, -1), ("rep", rep, 1.0), ("freq", freq, 0.0), ("pres", pres, 0.0),
+                                ("ids", ids, 0), ("pos", pos, 0), ("slots", slots, -1), ("last", last, 0),
                                 ("seeds", seeds, 0), ("spos", spos, 0), ("temp", temp, 0.0), ("ws", ws, -1),
                                 ("wq", wq, 0), ("cu", cu, int(cu[-1])), ("pfx", pfx if pfx is not None else [], 0),
                                 ("topk", topk if topk is not None else [], 0),
@@ -443,7 +486,8 @@ class LLMEngine:
 
     def __init__(self, model: LlamaModel, kv: PagedKVCache, max_batch: int = 256, max_prefill_tokens: int = 16384,
                  max_context: int | None = None, use_graphs: bool = True, multi_step: int = 8,
-                 admit_wait_s: float = 0.0, prefill_graphs: bool = True, prefix_sharing: bool = True):
+                 admit_wait_s: float = 0.0, prefill_graphs: bool = True, prefix_sharing: bool = True,
+                 penalty_slots: int | None = None):
         self.model, self.kv = model, kv
         # arrival batching window used by the loop that drives step() (EngineLoop):
         # an idle engine given less than a full prefill batch waits this long for more
@@ -467,6 +511,15 @@ class LLMEngine:
         self.hkv = model.hkv
         self.use_graphs = use_graphs and self.device.type == "cuda"
         self.multi_step = max(1, multi_step)
+        # penalty table (repetition / frequency / presence penalties): one slot per penalised
+        # request, ``penalty_slots`` of them (default max_batch: a slot can never be missing;
+        # 0: no table, no penalty kernel in the graphs, penalised requests refused). A TP replica
+        # has none: its vocabulary is sharded and penalised requests are refused at submit.
+        self.penalty_slots = max_batch if penalty_slots is None else max(0, int(penalty_slots))
+        self.penalties: PenaltyTable | None = None
+        if self.penalty_slots > 0 and model.tp.world == 1:
+            self.penalties = PenaltyTable(self.penalty_slots, model.cfg.vocab_size,
+                                          self.max_context + self.multi_step, device=self.device)
         self._active: _BucketState | None = None   # bucket whose device state matches self.running
         self.waiting: deque[GenRequest] = deque()
         self.running: list[GenRequest] = []
@@ -522,8 +575,9 @@ class LLMEngine:
 
     # ------------------------------------------------------------------ API
     def check_sampling(self, req: GenRequest) -> None:
-        """ValueError for top_k / top_p out of range, or set on a tensor-parallel replica (the
-        vocabulary is sharded there and no collective computes the global threshold)."""
+        """ValueError for top_k / top_p or a penalty out of range, or set on a tensor-parallel
+        replica (the vocabulary is sharded there and no collective computes the global threshold;
+        no penalty table is kept), or a penalty on an engine built without a penalty table."""
         k, p = req.top_k, req.top_p
         if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= k < 2 ** 31:
             raise ValueError(f"top_k must be an integer >= 0 (0 = off), got {k!r}")
@@ -531,6 +585,31 @@ class LLMEngine:
             raise ValueError(f"top_p must be in (0, 1] (1 = off), got {p!r}")
         if (k > 0 or p < 1) and self.model.tp.world > 1:
             raise ValueError("top_k / top_p are not supported with engine.tp > 1")
+        # penalties: the same on a TP replica (no table over a sharded vocabulary), and refused
+        # where the engine was built without a table (penalty_slots = 0)
+        r, f, pp = req.repetition_penalty, req.frequency_penalty, req.presence_penalty
+        if type(r) is float and type(f) is float and type(pp) is float and r == 1.0 and f == 0.0 and pp == 0.0:
+            return   # the defaults
+
+        def f32(v) -> float:   # the fp32 value the kernels read; NaN for what is no number
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                return math.nan
+            try:
+                return float(torch.tensor(float(v), dtype=torch.float32))
+            except OverflowError:
+                return math.nan
+
+        if not (math.isfinite(f32(r)) and f32(r) > 0):
+            raise ValueError(f"repetition_penalty must be a finite number > 0 (1 = off), got {r!r}")
+        if not math.isfinite(f32(f)):
+            raise ValueError(f"frequency_penalty must be a finite number (0 = off), got {f!r}")
+        if not math.isfinite(f32(pp)):
+            raise ValueError(f"presence_penalty must be a finite number (0 = off), got {pp!r}")
+        if req.penalised:
+            if self.model.tp.world > 1:
+                raise ValueError("penalties are not supported with engine.tp > 1")
+            if self.penalties is None:
+                raise ValueError("penalties are not supported with engine.penalty_slots = 0")
 
     def submit(self, req: GenRequest) -> GenRequest:
         if not req.prompt:
@@ -583,7 +662,12 @@ class LLMEngine:
         return len(self._pfx.pages) if self._pfx is not None else 0
 
     def _release(self, r: GenRequest) -> None:
-        """Return a request's own KV pages; shared prefix pages stay with the prefix."""
+        """Return a request's own KV pages and its penalty slot; shared prefix pages stay with
+        the prefix. The slot is not cleared: its next seeding does that, behind this request's
+        last decode step in stream order."""
+        if r.pslot >= 0:
+            self.penalties.give(r.pslot)
+            r.pslot = -1
         pf = r.prefix
         own = r.pages[len(pf.pages):] if pf is not None else r.pages
         if own:
@@ -803,6 +887,10 @@ class LLMEngine:
                         r.event.set()
                         continue
                     break
+                if r.penalised:
+                    if not self.penalties.free:   # only with penalty_slots < max_batch: wait for a reap
+                        break
+                    r.pslot = self.penalties.take()
                 r.pages = self.kv.allocator.alloc(need)
                 if shared:
                     r.pages = pf.pages + r.pages
@@ -864,9 +952,14 @@ class LLMEngine:
         seeds = [r.seed for r in batch]
         topk = [r.top_k for r in batch]
         topp = [r.top_p for r in batch]
+        pen = None
+        if any(r.pslot >= 0 for r in batch):
+            pen = ([r.pslot for r in batch], [r.repetition_penalty for r in batch],
+                   [r.frequency_penalty for r in batch], [r.presence_penalty for r in batch])
+            self._seed_penalties([r for r in batch if r.pslot >= 0])
         g = self._prefill_graph_for(len(ids), len(batch))
         if g is not None:
-            toks, ev = g.launch(ids, pos, slots, cu, ws, wq, last, temps, seeds, full, skip, topk, topp)
+            toks, ev = g.launch(ids, pos, slots, cu, ws, wq, last, temps, seeds, full, skip, topk, topp, pen)
             self.stats.prefill_graph_replays += 1
             self.stats.prefill_padded_tokens += g.T - len(ids)
         else:
@@ -876,6 +969,9 @@ class LLMEngine:
             pre = None if pfx is None else (self._pk, self._pv, t(pfx, torch.int32), pfx)
             fb = ForwardBatch(t(ids), t(pos), t(slots), True, t(last), seq_lens=lens, prefill_work=work, prefix=pre)
             logits = self.model.forward(fb, self.kv)
+            if pen is not None:
+                ops.sample_penalty(logits, t(pen[0], torch.int32), None, None, t(pen[1], torch.float32),
+                                   t(pen[2], torch.float32), t(pen[3], torch.float32), self.penalties)
             tk = self.model.sample(logits, t(temps, torch.float32), t(seeds), t(full), top_k=t(topk, torch.int32),
                                    top_p=t(topp, torch.float32))
             if dev.type == "cuda":
@@ -886,6 +982,18 @@ class LLMEngine:
             else:
                 toks, ev = tk.tolist(), None
         return _PendingPrefill(batch, toks, ev, t0, len(ids))
+
+    def _seed_penalties(self, reqs: list[GenRequest]) -> None:
+        """Clear the penalty slots of ``reqs`` and flag their prompts' tokens, eagerly, ahead of
+        the prefill on the same stream. The whole prompt: a request on the shared prefix
+        prefills only its own tokens, but the prefix's tokens are seen all the same."""
+        dev = self.device
+        cu = np.zeros(len(reqs) + 1, dtype=np.int32)
+        cu[1:] = np.cumsum([len(r.prompt) for r in reqs])
+        ids = np.concatenate([np.asarray(r.prompt, dtype=np.int64) for r in reqs])
+        slots = np.asarray([r.pslot for r in reqs], dtype=np.int32)
+        t = lambda x: torch.from_numpy(x).to(dev, non_blocking=True)  # noqa: E731
+        ops.penalty_seed(self.penalties, t(slots), t(ids), t(cu))
 
     def _prefill_graph(self, T: int) -> _PrefillGraph:
         g = self._prefill_g.get(T)

@@ -24,6 +24,7 @@ from __future__ import annotations
 
 import json
 import logging
+import math
 import threading
 import time
 import uuid
@@ -53,9 +54,46 @@ def _top_p(v) -> float:
     return float(v)
 
 
+def _number(name: str, v, lo: float = -math.inf, hi: float = math.inf, positive: bool = False) -> float:
+    """A finite JSON number in [lo, hi] (> 0 when ``positive``); booleans are not numbers."""
+    rng = "a number > 0" if positive else "a number" if lo == -math.inf else f"a number in [{lo:g}, {hi:g}]"
+    try:
+        x = float(v) if isinstance(v, (int, float)) and not isinstance(v, bool) else math.nan
+    except OverflowError:   # an integer beyond the floats
+        x = math.nan
+    if not math.isfinite(x) or not lo <= x <= hi or (positive and not x > 0):
+        raise ValueError(f"{name} must be {rng}, got {v!r}")
+    return x
+
+
+def _penalties(src: dict, ollama: bool) -> dict:
+    """repetition / frequency / presence penalty of an OpenAI body (``frequency_penalty`` and
+    ``presence_penalty`` in [-2, 2]; ``repetition_penalty``, the vLLM extension, > 0) or an
+    Ollama ``options`` map (``repeat_penalty`` > 0, ``presence_penalty``, ``frequency_penalty``;
+    ``repeat_last_n``: absent or -1 = the whole context, 0 = ``repeat_penalty`` off, anything
+    else is refused: no sliding window is built). Absent or null means off; an Ollama server's
+    implicit repeat_penalty 1.1 is not adopted (docs/PARITY.md)."""
+    kw = {}
+    lim = (-math.inf, math.inf) if ollama else (-2.0, 2.0)
+    rep_name = "repeat_penalty" if ollama else "repetition_penalty"
+    if src.get(rep_name) is not None:
+        kw["repetition_penalty"] = _number(rep_name, src[rep_name], positive=True)
+    for name in ("frequency_penalty", "presence_penalty"):
+        if src.get(name) is not None:
+            kw[name] = _number(name, src[name], *lim)
+    if ollama and src.get("repeat_last_n") is not None:
+        n = src["repeat_last_n"]
+        if isinstance(n, bool) or not isinstance(n, (int, float)) or n not in (-1, 0):
+            raise ValueError(f"repeat_last_n must be -1 (the whole context) or 0 (repeat_penalty off), got {n!r}: "
+                             "a sliding penalty window is not supported")
+        if n == 0:
+            kw.pop("repetition_penalty", None)
+    return kw
+
+
 def _sampling(body: dict, ollama: bool) -> dict:
-    """max_tokens / temperature / seed / top_k / top_p of an OpenAI body or an Ollama
-    ``options`` map (defaults: the AIProvider CRD's 500 tokens at T = 0.3). ``top_p`` is part
+    """max_tokens / temperature / seed / top_k / top_p and the penalties of an OpenAI body or an
+    Ollama ``options`` map (defaults: the AIProvider CRD's 500 tokens at T = 0.3). ``top_p`` is part
     of the OpenAI body and ``top_k`` the extension vLLM-compatible clients send; both are
     standard Ollama options. Absent or null means off: an Ollama server applies top_k 40 /
     top_p 0.9 to a request that names neither, this one does not (docs/PARITY.md)."""
@@ -72,6 +110,7 @@ def _sampling(body: dict, ollama: bool) -> dict:
             kw["top_k"] = _top_k(src["top_k"])
         if src.get("top_p") is not None:
             kw["top_p"] = _top_p(src["top_p"])
+        kw.update(_penalties(src, ollama))
         n_choices = int(body.get("n", 1) or 1)
     except (TypeError, ValueError) as e:
         raise BadRequest(f"bad sampling parameter: {e}") from None
@@ -201,7 +240,8 @@ class CompatServer:
                     return self._send(400, {"error": {"message": str(e), "type": "invalid_request_error"}})
                 except Exception as e:  # noqa: BLE001
                     msg = str(e)
-                    if "exceeds max_context" in msg or "top_k / top_p are not supported" in msg:
+                    if "exceeds max_context" in msg or "top_k / top_p are not supported" in msg \
+                            or "penalties are not supported" in msg:
                         return self._send(400, {"error": {"message": msg, "type": "invalid_request_error"}})
                     log.error("request %s failed: %s", self.path, e)
                     return self._send(504 if "timed out" in msg else 500, {"error": {"message": msg}})

@@ -19,7 +19,7 @@ from .gemm import (BLAS_CALLS, BLAS_PLANNED, GEMM_DECODE_M, GU_BLOCK, LM_HEAD_MI
 
 __all__ = [
     "rmsnorm", "silu_mul", "embedding", "rope_kv", "attn_prefill", "attn_decode", "attn_decode_rope", "sample",
-    "sample_threshold",
+    "sample_threshold", "penalty_seed", "sample_penalty",
     "kernels", "patterns", "native_available", "reference", "prefill_work_list", "prefill_block_q", "prefill_variant", "decode_splits",
     "decode_workspace", "linear", "gemm_plan", "gemm_table", "gate_up_silu", "interleave_gate_up",
     "quantize_fp8", "silu_quantize_fp8", "linear_fp8", "fp8_plan", "SplitK", "linear_tile", "tile_ok", "BLAS_CALLS",
@@ -402,6 +402,33 @@ def sample_threshold(logits: torch.Tensor, temperature: torch.Tensor, top_k: tor
     o = out if out is not None else torch.empty(rows, dtype=torch.float32, device=logits.device)
     kernels().sample_threshold(logits, temperature, top_k, top_p, o, out_kept)
     return o
+
+
+def penalty_seed(table, slots: torch.Tensor, ids: torch.Tensor, cu: torch.Tensor) -> None:
+    """Clear the penalty-table slots ``slots`` (int32) and flag the tokens of their requests'
+    whole prompts: ``ids`` (int64) packed, request b's at ``ids[cu[b]:cu[b + 1]]`` (``cu`` int32).
+    ``table``: the ``cnt`` / ``lst`` / ``n`` tensors (models/penalty.py PenaltyTable). Slots are
+    distinct; semantics: ``reference.penalty_seed``."""
+    if not table.cnt.is_cuda:
+        reference.penalty_seed(table.cnt, table.lst, table.n, slots, ids, cu)
+        return
+    kernels().penalty_seed(slots, ids, cu, table.cnt, table.lst, table.n)
+
+
+def sample_penalty(logits: torch.Tensor, pslot: torch.Tensor, last_tok: torch.Tensor | None,
+                   ctx: torch.Tensor | None, rep: torch.Tensor, freq: torch.Tensor, pres: torch.Tensor,
+                   table) -> torch.Tensor:
+    """Repetition / frequency / presence penalties on ``logits`` [rows, vocab] in place, before
+    temperature and top-k / top-p (semantics: ``reference.sample_penalty``). Row i uses slot
+    ``pslot[i]`` (int32; < 0: no penalty, the row is not read) of ``table``; ``rep`` / ``freq`` /
+    ``pres`` fp32 per row. With ``last_tok`` (int64 per row: the last sampled token, which a
+    decode step feeds in) that token is counted first; ``ctx`` (int32 per row) == 0 marks a
+    padding row. Each slot appears on at most one row."""
+    if not logits.is_cuda:
+        reference.sample_penalty(logits, pslot, last_tok, ctx, rep, freq, pres, table.cnt, table.lst, table.n)
+        return logits
+    kernels().sample_penalty(logits, pslot, last_tok, ctx, rep, freq, pres, table.cnt, table.lst, table.n)
+    return logits
 
 
 def sample(logits: torch.Tensor, temperature: torch.Tensor, seeds: torch.Tensor, positions: torch.Tensor,

@@ -296,6 +296,73 @@ def sample_shard(logits: torch.Tensor, temperature: torch.Tensor, seeds: torch.T
     return out.to(logits.device), val.to(logits.device)
 
 
+PROMPT_BIT = -2 ** 31      # bit 31 of a penalty-table word (int32): the token is in the prompt
+COUNT_MASK = 2 ** 31 - 1    # bits 0-30: how often the token was generated
+
+
+def penalty_seed(cnt: torch.Tensor, lst: torch.Tensor, n: torch.Tensor, slots: torch.Tensor, ids: torch.Tensor,
+                 cu: torch.Tensor) -> None:
+    """Clear the penalty-table slots ``slots`` (walking each one's list) and flag the tokens of
+    the packed prompts ``ids[cu[b]:cu[b + 1]]`` with bit 31, listing each distinct one once. Ids
+    outside the table's vocabulary and slots < 0 are ignored. The table is int32 ``cnt``
+    [slots, vocab], ``lst`` [slots, cap], ``n`` [slots] (docs/PARITY.md "Sampling: penalties")."""
+    V, cap = cnt.shape[1], lst.shape[1]
+    off = [int(x) for x in cu]
+    for b, s in enumerate(int(x) for x in slots):
+        if not 0 <= s < cnt.shape[0]:
+            continue
+        k = min(max(int(n[s]), 0), cap)
+        old = lst[s, :k].long()
+        cnt[s, old[(old >= 0) & (old < V)]] = 0
+        p = ids[max(off[b], 0):off[b + 1]].long()
+        u = torch.unique(p[(p >= 0) & (p < V)])[:cap]
+        cnt[s, u] = PROMPT_BIT
+        lst[s, :u.numel()] = u.to(lst.dtype)
+        n[s] = u.numel()
+
+
+def sample_penalty(logits: torch.Tensor, pslot: torch.Tensor, last_tok: torch.Tensor | None, ctx: torch.Tensor | None,
+                   rep: torch.Tensor, freq: torch.Tensor, pres: torch.Tensor, cnt: torch.Tensor, lst: torch.Tensor,
+                   n: torch.Tensor) -> None:
+    """Repetition / frequency / presence penalties on ``logits`` in place (vLLM / HF semantics,
+    docs/PARITY.md "Sampling: penalties"). Row i uses table slot ``pslot[i]`` (< 0, or ``ctx[i]``
+    == 0 when ``ctx`` is given: untouched). With ``last_tok`` the row's token is counted first
+    (a new token is appended to the slot's list; a full list leaves the table as it is). Then,
+    for every token t of the list with word w = cnt[slot, t] and c = w & COUNT_MASK::
+
+        y = x (fp32);  rep != 1:  y = y / rep if y > 0 else y * rep;  c > 0:  y = y - (freq * c + pres)
+
+    each operation rounded to fp32 on its own, the result rounded to the logits' dtype. A NaN
+    logit keeps its bytes."""
+    V, cap = logits.shape[1], lst.shape[1]
+    for row, s in enumerate(int(x) for x in pslot):
+        if not 0 <= s < cnt.shape[0] or (ctx is not None and int(ctx[row]) == 0):
+            continue
+        if last_tok is not None:
+            t = int(last_tok[row])
+            if 0 <= t < cnt.shape[1]:
+                w = int(cnt[s, t])
+                if w == 0:
+                    k = int(n[s])
+                    if 0 <= k < cap:
+                        lst[s, k] = t
+                        n[s] = k + 1
+                        cnt[s, t] = 1
+                elif (w & COUNT_MASK) != COUNT_MASK:
+                    cnt[s, t] = w + 1
+        k = min(max(int(n[s]), 0), cap)
+        idx = lst[s, :k].long()
+        idx = idx[(idx >= 0) & (idx < min(V, cnt.shape[1]))]
+        c = cnt[s, idx] & COUNT_MASK
+        x = logits[row, idx]
+        y = x.float()
+        r, f, p = rep[row].float(), freq[row].float(), pres[row].float()
+        if float(r) != 1.0:
+            y = torch.where(y > 0, y / r, y * r)
+        y = torch.where(c > 0, y - (f * c.float() + p), y)
+        logits[row, idx] = torch.where(torch.isnan(x), x, y.to(logits.dtype))
+
+
 def sample(logits: torch.Tensor, temperature: torch.Tensor, seeds: torch.Tensor,
            positions: torch.Tensor) -> torch.Tensor:
     return sample_shard(logits, temperature, seeds, positions)[0]

@@ -10,6 +10,10 @@ minimum of the rounds' microseconds per call.
 
 defaults - plain is what an existing decode step pays; the last two are the price of the
 feature. One JSON line per arm on stdout (and appended to --out).
+
+--penalties measures the repetition / frequency / presence penalty kernel the same way, three
+arms: the defaults step; the same behind sample_penalty with no row holding a slot (what every
+decode step launches now); the same with every row penalised over --seen distinct tokens.
 """
 import argparse
 import json
@@ -30,6 +34,10 @@ ap.add_argument("--temperature", type=float, default=0.8)
 ap.add_argument("--rounds", type=int, default=12)
 ap.add_argument("--calls", type=int, default=20, help="calls per arm per round")
 ap.add_argument("--out", default=None)
+ap.add_argument("--penalties", action="store_true",
+                help="the penalty arms in place of the filter arms: the defaults step, the same behind the "
+                     "penalty kernel with every row off, and with every row on")
+ap.add_argument("--seen", type=int, default=1100, help="distinct seen tokens per row of the rows-on arm")
 a = ap.parse_args()
 
 B = a.batch
@@ -46,23 +54,59 @@ def filt(k, p):
                 top_p=torch.full((B,), p, dtype=torch.float32, device="cuda"), thr=thr)
 
 
-arms = {"plain": {}, "defaults": filt(0, 1.0), "top_p": filt(0, 0.9), "top_k+top_p": filt(40, 0.9)}
-for kw in arms.values():
+def penalty_arm(on: bool):
+    """The decode step's count-and-apply kernel in front of the defaults step: every row
+    without a slot (what a step with no penalised request pays), or every row with its own
+    slot holding --seen distinct tokens (the flagship's context) at r 1.1, f 0.2, p 0.3. The
+    token fed in is one already listed, so every call walks a list of the same length."""
+    from operator_amd.models.penalty import PenaltyTable
+
+    tb = PenaltyTable(B, a.vocab, a.seen + 64, device="cuda")
+    g = torch.Generator().manual_seed(1)
+    for s in range(B):
+        toks = torch.randperm(a.vocab, generator=g)[:a.seen].to(torch.int32).cuda()
+        tb.lst[s, :a.seen] = toks
+        tb.cnt[s, toks.long()] = 3
+    tb.n.fill_(a.seen)
+    pslot = (torch.arange(B, dtype=torch.int32) if on else torch.full((B,), -1, dtype=torch.int32)).cuda()
+    last = tb.lst[:, 0].long().contiguous()
+    ctx = torch.full((B,), 1100, dtype=torch.int32, device="cuda")
+    rep, freq, pres = (torch.full((B,), v, dtype=torch.float32, device="cuda") for v in (1.1, 0.2, 0.3))
+    return lambda: ops.sample_penalty(x, pslot, last, ctx, rep, freq, pres, tb)
+
+
+if a.penalties:
+    bench = "sampler_penalty"
+    arms = {"defaults": (None, filt(0, 1.0)), "penalty_kernel_rows_off": (penalty_arm(False), filt(0, 1.0)),
+            f"penalty_rows_on_{a.seen}_seen": (penalty_arm(True), filt(0, 1.0))}
+else:
+    bench = "sampler_filter"
+    arms = {"plain": (None, {}), "defaults": (None, filt(0, 1.0)), "top_p": (None, filt(0, 0.9)),
+            "top_k+top_p": (None, filt(40, 0.9))}
+
+
+def call(pre, kw):
+    if pre is not None:
+        pre()
+    ops.sample(x, t, sd, ps, out=out, **kw)
+
+
+for pre, kw in arms.values():
     for _ in range(3):
-        ops.sample(x, t, sd, ps, out=out, **kw)
+        call(pre, kw)
 torch.cuda.synchronize()
 us = {n: [] for n in arms}
 for _ in range(a.rounds):
-    for n, kw in arms.items():
+    for n, (pre, kw) in arms.items():
         e0, e1 = torch.cuda.Event(True), torch.cuda.Event(True)
         e0.record()
         for _ in range(a.calls):
-            ops.sample(x, t, sd, ps, out=out, **kw)
+            call(pre, kw)
         e1.record()
         torch.cuda.synchronize()
         us[n].append(e0.elapsed_time(e1) / a.calls * 1e3)
 for n, v in us.items():
-    line = json.dumps({"bench": "sampler_filter", "arm": n, "batch": B, "vocab": a.vocab, "scale": a.scale,
+    line = json.dumps({"bench": bench, "arm": n, "batch": B, "vocab": a.vocab, "scale": a.scale,
                        "temperature": a.temperature, "rounds": a.rounds, "calls_per_round": a.calls,
                        "us_median": round(statistics.median(v), 1), "us_min": round(min(v), 1),
                        "us_max": round(max(v), 1)})
