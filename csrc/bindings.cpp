@@ -674,6 +674,45 @@ void sample_threshold(const at::Tensor& logits, const at::Tensor& temperature, c
                             ptr<float>(thr), optr<int>(kept), cur_stream()));
 }
 
+// Log-probabilities of the sampled tokens and of each row's most likely tokens (kernels.h sample_logprobs):
+// tok_lp [rows, C], top_lp / top_id [rows, C, kLogprobsMax], written at column step[0] % C (0 without step).
+void sample_logprobs(const at::Tensor& logits, const at::Tensor& nlp, const c10::optional<at::Tensor>& ctx,
+                     const at::Tensor& tokens, const c10::optional<at::Tensor>& step, at::Tensor& tok_lp,
+                     at::Tensor& top_lp, at::Tensor& top_id) {
+  CHECK_DEV(logits);
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && logits.stride(0) >= logits.size(1),
+              "logits must be [rows, vocab] row-major");
+  TORCH_CHECK(logits.scalar_type() == at::kBFloat16 || logits.scalar_type() == at::kFloat, "logits dtype");
+  TORCH_CHECK(logits.size(1) < (int64_t(1) << 31) - 1024, "logits have too many columns");
+  const int64_t rows = logits.size(0);
+  for (const at::Tensor* t : {&nlp, &tokens, (const at::Tensor*)&tok_lp, (const at::Tensor*)&top_lp,
+                              (const at::Tensor*)&top_id}) {
+    CHECK_DEV(*t); CHECK_CONTIG(*t);
+    TORCH_CHECK(t->device() == logits.device(), "sample_logprobs: operands on one device");
+  }
+  CHECK_DT(nlp, at::kInt); CHECK_DT(tokens, at::kLong);
+  CHECK_DT(tok_lp, at::kFloat); CHECK_DT(top_lp, at::kFloat); CHECK_DT(top_id, at::kInt);
+  TORCH_CHECK(nlp.numel() == rows && tokens.numel() == rows, "sample_logprobs per-row tensor shape");
+  TORCH_CHECK(tok_lp.dim() == 2 && tok_lp.size(0) == rows && tok_lp.size(1) >= 1, "tok_lp must be [rows, C]");
+  const int64_t C = tok_lp.size(1);
+  TORCH_CHECK(C < (int64_t(1) << 20) && rows < (int64_t(1) << 31), "sample_logprobs: outputs too large");
+  for (const at::Tensor* t : {(const at::Tensor*)&top_lp, (const at::Tensor*)&top_id})
+    TORCH_CHECK(t->dim() == 3 && t->size(0) == rows && t->size(1) == C && t->size(2) == oamd::kLogprobsMax,
+                "top_lp / top_id must be [rows, C, ", oamd::kLogprobsMax, "]");
+  if (ctx.has_value()) {
+    CHECK_DEV(*ctx); CHECK_DT(*ctx, at::kInt); CHECK_CONTIG(*ctx);
+    TORCH_CHECK(ctx->numel() == rows && ctx->device() == logits.device(), "ctx shape / device");
+  }
+  if (step.has_value()) {
+    CHECK_DEV(*step); CHECK_DT(*step, at::kLong);
+    TORCH_CHECK(step->numel() == 1 && step->device() == logits.device(), "step shape / device");
+  }
+  const c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
+  RC(oamd::sample_logprobs(logits.data_ptr(), logits.scalar_type() == at::kBFloat16, logits.stride(0), (int)rows,
+                           (int)logits.size(1), ptr<int>(nlp), optr<int>(ctx), ptr<int64_t>(tokens), optr<int64_t>(step),
+                           (int)C, ptr<float>(tok_lp), ptr<float>(top_lp), ptr<int>(top_id), cur_stream()));
+}
+
 }  // namespace
 
 // Launch an instantiated hipGraph `count` times back to back on `stream` with the
@@ -756,6 +795,10 @@ PYBIND11_MODULE(_C, m) {
   m.def("sample_penalty", &sample_penalty, pybind11::arg("logits"), pybind11::arg("pslot"), pybind11::arg("last_tok"),
         pybind11::arg("ctx"), pybind11::arg("rep"), pybind11::arg("freq"), pybind11::arg("pres"), pybind11::arg("cnt"),
         pybind11::arg("lst"), pybind11::arg("n"));
+  m.def("sample_logprobs", &sample_logprobs, pybind11::arg("logits"), pybind11::arg("nlp"), pybind11::arg("ctx"),
+        pybind11::arg("tokens"), pybind11::arg("step"), pybind11::arg("tok_lp"), pybind11::arg("top_lp"),
+        pybind11::arg("top_id"));
+  m.attr("LOGPROBS_MAX") = oamd::kLogprobsMax;
   m.def("graph_launch", &graph_launch, pybind11::arg("graph_exec"), pybind11::arg("count"), pybind11::arg("stream"));
   register_scan_bindings(m);
   register_comm_bindings(m);

@@ -163,6 +163,17 @@ int sample_penalty(void* logits, bool logits_bf16, int64_t stride, int rows, int
                    const int64_t* last_tok, const int* ctx, const float* rep, const float* freq, const float* pres,
                    PenaltyTable table, hipStream_t stream);
 
+// Log-probabilities of sampled tokens (logprob.hip, docs/PARITY.md "Sampling: logprobs"). Per row with
+// nlp[row] >= 0 (and ctx[row] != 0 when ctx is given), at column c = step[0] % C (0 without step):
+// tok_lp[row][c] = x[tokens[row]] - lse, lse the log-sum-exp of the row's non-NaN logits, and the first
+// N = min(nlp[row], kLogprobsMax) entries of top_id / top_lp [row][c][kLogprobsMax]: the N most likely
+// tokens by (logit descending, id ascending) and their log-probabilities, id -1 / -inf where the row
+// has fewer non-NaN logits. Every other byte of the outputs is left alone; other rows are not read.
+constexpr int kLogprobsMax = 20;
+int sample_logprobs(const void* logits, bool logits_bf16, int64_t stride, int rows, int vocab, const int* nlp,
+                    const int* ctx, const int64_t* tokens, const int64_t* step, int C, float* tok_lp, float* top_lp,
+                    int* top_id, hipStream_t stream);
+
 // One-shot all-reduce over peer-mapped fine-grained buffers (allreduce.hip).
 size_t car_buffer_bytes(size_t cap_bytes, int world);
 int car_alloc(size_t cap_bytes, int world, void** base, void* handle_out /* 64 B hipIpcMemHandle_t */);

@@ -7,15 +7,9 @@
 // same tokens and the kernel needs no RNG state on the device.
 #include "common.h"
 #include "kernels.h"
+#include "sample_row.h"
 
 namespace oamd {
-
-template <typename T>
-__device__ __forceinline__ float load_logit(const T* p, int64_t i);
-template <>
-__device__ __forceinline__ float load_logit<float>(const float* p, int64_t i) { return p[i]; }
-template <>
-__device__ __forceinline__ float load_logit<bf16_t>(const bf16_t* p, int64_t i) { return bf2f(p[i]); }
 
 __device__ __forceinline__ void argmax_merge(float& bv, int& bi, float v, int i) {
   if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
@@ -119,56 +113,6 @@ __global__ void __launch_bounds__(1024) sample_kernel(const T* __restrict__ logi
 // integer key of the logit; a bf16 logit has 16 significant key bits, so two passes per
 // select, an fp32 logit four.
 // ---------------------------------------------------------------------------------------------
-
-// Sign bit flipped for non-negatives, every bit for negatives: unsigned key order == float
-// order, -inf lowest, +inf highest. -0 and +0 are one value. (NaN is never given a key.)
-__device__ __forceinline__ uint32_t logit_key(float x) {
-  uint32_t b = __float_as_uint(x);
-  if (x == 0.f) b = 0u;
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-// Inverse of logit_key(x) >> (32 - 8 NB) for a logit whose low 32 - 8 NB bits are zero.
-template <int NB>
-__device__ __forceinline__ float key_logit(uint32_t kn) {
-  constexpr int SH = 32 - 8 * NB;
-  const uint32_t full = kn << SH;
-  const uint32_t b = (full & 0x80000000u) ? (full ^ 0x80000000u) : (~full & (0xffffffffu << SH));
-  return __uint_as_float(b);
-}
-
-// f(x) for every column of a row, in sample_kernel's order: 16-B loads over the aligned body
-// (four in flight per thread), scalar tail; a row off a 16-B boundary is all tail.
-template <typename T, typename F>
-__device__ __forceinline__ void walk_row(const T* __restrict__ lr, int vocab, F&& f) {
-  constexpr int VEC = 16 / static_cast<int>(sizeof(T));
-  const int nv = (reinterpret_cast<uintptr_t>(lr) & 15) == 0 ? vocab / VEC : 0;
-  auto f16 = [&](const uint4& raw) {
-    const uint32_t wv[4] = {raw.x, raw.y, raw.z, raw.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if constexpr (sizeof(T) == 2) {
-        f(__uint_as_float(wv[k] << 16));
-        f(__uint_as_float(wv[k] & 0xffff0000u));
-      } else {
-        f(__uint_as_float(wv[k]));
-      }
-    }
-  };
-  constexpr int UNR = 4;
-  const uint4* lv = reinterpret_cast<const uint4*>(lr);
-  const int step = blockDim.x;
-  int v0 = threadIdx.x;
-  for (; v0 + (UNR - 1) * step < nv; v0 += UNR * step) {
-    uint4 raw[UNR];
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) raw[u] = lv[v0 + u * step];
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) f16(raw[u]);
-  }
-  for (int v = v0; v < nv; v += step) f16(lv[v]);
-  for (int i = nv * VEC + threadIdx.x; i < vocab; i += blockDim.x) f(load_logit<T>(lr, i));
-}
 
 // One 1024-thread block per row. thr[row] = max(tau_k, tau_p):
 //   tau_k: the top_k-th largest logit (ties at it are all kept); off for top_k <= 0 or >= vocab;

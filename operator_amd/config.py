@@ -146,6 +146,9 @@ class EngineCfg(BaseModel):
     # request in flight, 4 x vocab bytes each): None = max_batch, 0 = no table, no penalty kernel in
     # the graphs, and requests that set a penalty are refused
     penalty_slots: int | None = None
+    # the log-probability kernel behind the sampler in every graph (requests that do not ask leave it
+    # at once); false: no kernel in the graphs, and requests that set logprobs are refused
+    logprobs: bool = True
     ignore_eos: bool = False
 
 

@@ -441,17 +441,20 @@ class ExplainEngine:
     def complete(self, ids: list[int], max_tokens: int = 500, temperature: float = 0.3, seed: int | None = None,
                  timeout_s: float | None = None, top_k: int = 0, top_p: float = 1.0,
                  repetition_penalty: float = 1.0, frequency_penalty: float = 0.0,
-                 presence_penalty: float = 0.0) -> dict:
+                 presence_penalty: float = 0.0, logprobs: int = -1) -> dict:
         """Generate from raw prompt token ids on the same continuous batch as the
         explanations (the OpenAI / Ollama endpoints of engine/server.py). ``top_k`` (0 = off) /
         ``top_p`` (1 = off): top-k / nucleus sampling. ``repetition_penalty`` (1 = off) /
         ``frequency_penalty`` / ``presence_penalty`` (0 = off): penalties on tokens already seen
-        (docs/PARITY.md "Sampling: penalties"). Raises ExplainError on a timeout, an
+        (docs/PARITY.md "Sampling: penalties"). ``logprobs`` (-1 = off; 0..20 alternatives per
+        position) adds a ``"logprobs"`` entry to the result: per generated token ``token_id``,
+        ``token`` (its text), ``bytes``, ``logprob`` and ``top``, the alternatives with the same
+        fields, most likely first (docs/PARITY.md "Sampling: logprobs"). Raises ExplainError on a timeout, an
         engine error, a prompt the engine cannot hold or sampling parameters it rejects."""
         req = GenRequest(list(ids), max_tokens=max(1, int(max_tokens)), temperature=max(0.0, float(temperature)),
                          seed=self._seed(ids) if seed is None else int(seed), ignore_eos=self.ignore_eos,
                          top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
-                         frequency_penalty=frequency_penalty, presence_penalty=presence_penalty)
+                         frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, logprobs=logprobs)
         want = req.max_tokens
         t0 = time.perf_counter()
         try:
@@ -464,8 +467,25 @@ class ExplainEngine:
             raise ExplainError(f"completion timed out after {timeout_s}s")
         if req.error:
             raise ExplainError(req.error)
-        return {"text": req.text if req.text is not None else self.tok.decode(req.output),
-                "prompt_tokens": len(req.prompt),
-                "completion_tokens": len(req.output),
-                "finish_reason": "length" if len(req.output) >= min(want, req.max_tokens) else "stop",
-                "latency_ms": round((req.t_done - t0) * 1e3, 3)}
+        out = {"text": req.text if req.text is not None else self.tok.decode(req.output),
+               "prompt_tokens": len(req.prompt),
+               "completion_tokens": len(req.output),
+               "finish_reason": "length" if len(req.output) >= min(want, req.max_tokens) else "stop",
+               "latency_ms": round((req.t_done - t0) * 1e3, 3)}
+        if req.logprobs >= 0:
+            out["logprobs"] = [{**self._token_entry(t, lp), "top": [self._token_entry(a, b) for a, b in top]}
+                               for t, lp, top in zip(req.output, req.token_logprobs, req.top_logprobs)]
+        return out
+
+    def _token_entry(self, tid: int, logprob: float) -> dict:
+        """One token of a ``logprobs`` result: its text as ``decode`` gives it and its bytes, from
+        the tokenizer's byte table where it has one (a token may hold part of a UTF-8 sequence),
+        else the UTF-8 of the text."""
+        tok = self.tok
+        text = tok.decode([tid])
+        table = tok.byte_table()
+        if table is None:
+            raw = text.encode("utf-8")
+        else:
+            raw = b"" if tid in (tok.bos_id, tok.eos_id) else table[tid % tok.n_vocab]
+        return {"token_id": int(tid), "token": text, "bytes": list(raw), "logprob": float(logprob)}

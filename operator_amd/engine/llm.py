@@ -24,6 +24,10 @@ hipGraph-captured decode steps.
   slot is seeded with the whole prompt ahead of the prefill; every decode step counts the
   token it feeds in and penalises the logits inside the graph, between lm_head and sampler
   (``ops.sample_penalty``). Rows of requests without a penalty carry slot -1.
+* Log-probabilities (``GenRequest.logprobs``): behind the sampler every prefill and decode step
+  runs ``ops.sample_logprobs`` over the logits the sampler was handed, inside the graph. It only
+  reads them; rows of requests that did not ask carry -1 and leave it at once, and its outputs
+  are copied to the host only for a window that holds a request that asked.
 """
 from __future__ import annotations
 
@@ -66,12 +70,19 @@ class GenRequest:
     repetition_penalty: float = 1.0   # seen in the prompt or generated: logit / r if > 0 else * r (1 = off)
     frequency_penalty: float = 0.0    # generated c > 0 times: logit - f * c (0 = off)
     presence_penalty: float = 0.0     # ... and - p (0 = off)
+    # log-probabilities (docs/PARITY.md "Sampling: logprobs"): -1 off, 0 the sampled token's only,
+    # 1..20 that many most likely alternatives per position as well
+    logprobs: int = -1
     rid: int = -1
     # runtime state
     pages: list[int] = field(default_factory=list)
     prefix: "_SharedPrefix | None" = None   # shared prompt-prefix pages at the head of ``pages``
     pslot: int = -1                # penalty-table slot from admission to reaping (-1: no penalty set)
     output: list[int] = field(default_factory=list)
+    # with logprobs >= 0, in step with ``output``: the log-probability of each token, and the
+    # ``logprobs`` most likely (token id, log-probability) pairs of its position, most likely first
+    token_logprobs: list[float] = field(default_factory=list)
+    top_logprobs: list[list[tuple[int, float]]] = field(default_factory=list)
     done: bool = False
     cancelled: bool = False
     done_pending: bool = False     # EOS seen inside a multi-step window
@@ -130,6 +141,7 @@ class _Window:
     host: torch.Tensor
     event: object
     s0: int = 0           # hist column of the window's first step (columns wrap mod multi_step)
+    lp: tuple | None = None   # (tok_lp, top_lp, top_id) of the window's rows when one of them asked
 
 
 def _prefill_bucket_sizes(max_tokens: int) -> list[int]:
@@ -187,13 +199,16 @@ class _BucketState:
                       ("topk", (bp,), torch.int32), ("topp", (bp,), torch.float32),
                       # penalty-table slot (-1: none) and the three penalties of each row
                       ("pslot", (bp,), torch.int32), ("rep", (bp,), torch.float32), ("freq", (bp,), torch.float32),
-                      ("pres", (bp,), torch.float32), ("bt", (bp, mp), torch.int32))
+                      ("pres", (bp,), torch.float32),
+                      # entries of the log-probability list each row asked for (-1: none, not even its token's)
+                      ("nlp", (bp,), torch.int32), ("bt", (bp, mp), torch.int32))
         self._nbytes = sum(int(np.prod(s)) * torch.empty((), dtype=dt).element_size() for _, s, dt in self._spec)
         self._buf = torch.zeros(self._nbytes, dtype=torch.uint8, device=dev)
         for n, t in self._views(self._buf).items():
             setattr(self, n, t)
         self.pslot.fill_(-1)   # no row owns a penalty slot before the first load
         self.rep.fill_(1.0)
+        self.nlp.fill_(-1)     # ... nor asks for log-probabilities
         self.hist = torch.zeros(bp, eng.multi_step, dtype=torch.long, device=dev)
         # steps replayed since the last load: the device counter (``step``, bumped by every
         # replay; hist column = step % multi_step) mirrored on the host, so a window needs
@@ -203,6 +218,13 @@ class _BucketState:
         self.slots = torch.zeros(bp, dtype=torch.long, device=dev)   # per step: cache slot of each row's token
         self.spos = torch.zeros(bp, dtype=torch.long, device=dev)    # per step: sampler stream position
         self.thr = torch.zeros(bp, dtype=torch.float32, device=dev)  # per step: top-k / top-p threshold of each row
+        # log-probabilities of the rows that ask, one column per step of a window like ``hist``
+        self.tok_lp = self.top_lp = self.top_id = None
+        if eng.logprobs:
+            C, L = eng.multi_step, ops.LOGPROBS_MAX
+            self.tok_lp = torch.zeros(bp, C, dtype=torch.float32, device=dev)
+            self.top_lp = torch.zeros(bp, C, L, dtype=torch.float32, device=dev)
+            self.top_id = torch.zeros(bp, C, L, dtype=torch.int32, device=dev)
 
     def _views(self, buf: torch.Tensor) -> dict:
         out, off = {}, 0
@@ -224,7 +246,9 @@ class _BucketState:
         v["topp"][:] = 1.0   # padding rows: unfiltered (topk 0)
         v["pslot"][:] = -1   # ... and unpenalised (freq / pres 0)
         v["rep"][:] = 1.0
+        v["nlp"][:] = -1     # ... and without log-probabilities
         if n:
+            v["nlp"][:n] = np.fromiter((r.logprobs for r in reqs), dtype=np.int32, count=n)
             v["pslot"][:n] = np.fromiter((r.pslot for r in reqs), dtype=np.int32, count=n)
             v["rep"][:n] = np.fromiter((r.repetition_penalty for r in reqs), dtype=np.float32, count=n)
             v["freq"][:n] = np.fromiter((r.frequency_penalty for r in reqs), dtype=np.float32, count=n)
@@ -293,6 +317,10 @@ class _DecodeGraph:
         # threshold kernel + filtered sampler in every graph: rows at the defaults (top_k 0,
         # top_p 1) leave the first at once with thr = -inf and sample as before
         tok = e.model.sample(logits, st.temp, st.seeds, spos, top_k=st.topk, top_p=st.topp, thr=st.thr)
+        if e.logprobs:
+            # before the advance: st.step is still this step's column and st.ctx this step's padding
+            # mark. Rows that did not ask (nlp -1) and padding rows (ctx 0) leave it at once.
+            ops.sample_logprobs(logits, st.nlp, st.ctx, tok, st.step, st.tok_lp, st.top_lp, st.top_id)
         if gpu:
             ops.kernels().decode_advance(tok, st.ids, st.hist, st.pos, st.ctx, st.step)
         else:
@@ -306,14 +334,15 @@ class _DecodeGraph:
         # warm up on a side stream (allocator + hipBLASLt heuristics), then capture; the
         # state is snapshotted and restored so capture never perturbs live rows
         st = self.st
-        live = (st.ids, st.pos, st.ctx, st.step, st.pslot)
+        live = (st.ids, st.pos, st.ctx, st.step, st.pslot, st.nlp)
         snap = [t.clone() for t in live]
         s = torch.cuda.Stream(device=self.eng.device)
         s.wait_stream(torch.cuda.current_stream())
         saved_ctx = st.ctx.clone()
         st.ctx.zero_()  # all rows padding while warming up: no KV writes
         st.pslot.fill_(-1)   # ... and no row with a penalty slot: the table is never touched
-        s.wait_stream(torch.cuda.current_stream())   # the two fills above come before the warm-up runs
+        st.nlp.fill_(-1)     # ... or asking for log-probabilities
+        s.wait_stream(torch.cuda.current_stream())   # the fills above come before the warm-up runs
         with torch.cuda.stream(s):
             for _ in range(2):
                 st.step.zero_()
@@ -359,7 +388,8 @@ class _PrefillGraph:
         spec = (("ids", T, i64), ("pos", T, i64), ("slots", T, i64), ("last", S, i64), ("seeds", S, i64),
                 ("spos", S, i64), ("cu", S + 1, i32), ("ws", self.W, i32), ("wq", self.W, i32),
                 ("temp", S, torch.float32), ("pfx", S, i32), ("topk", S, i32), ("topp", S, torch.float32),
-                ("pslot", S, i32), ("rep", S, torch.float32), ("freq", S, torch.float32), ("pres", S, torch.float32))
+                ("pslot", S, i32), ("rep", S, torch.float32), ("freq", S, torch.float32), ("pres", S, torch.float32),
+                ("nlp", S, i32))
         self._layout, off = [], 0
         for n, k, dt in spec:
             isz = torch.empty((), dtype=dt).element_size()
@@ -376,6 +406,12 @@ class _PrefillGraph:
         self._hbufs = [torch.zeros(off, dtype=torch.uint8).pin_memory() for _ in range(2)]
         self.hosts = [self._views(b) for b in self._hbufs]
         self.outs = [torch.zeros(S, dtype=i64).pin_memory() for _ in range(2)]
+        # log-probabilities of the first tokens (one column); pinned copies made at the first need
+        self.lp = self.lp_outs = None
+        if eng.logprobs:
+            L = ops.LOGPROBS_MAX
+            self.lp = (torch.zeros(S, 1, dtype=torch.float32, device=dev),
+                       torch.zeros(S, 1, L, dtype=torch.float32, device=dev), torch.zeros(S, 1, L, dtype=i32, device=dev))
         self.events: list = [None, None]
         self._i = 0
         self.graph: torch.cuda.CUDAGraph | None = None
@@ -398,13 +434,16 @@ class _PrefillGraph:
             ops.sample_penalty(logits, d["pslot"], None, None, d["rep"], d["freq"], d["pres"], e.penalties)
         self.tok = e.model.sample(logits, d["temp"], d["seeds"], d["spos"], top_k=d["topk"], top_p=d["topp"],
                                   thr=self.thr)
+        if e.logprobs:
+            ops.sample_logprobs(logits, d["nlp"], None, self.tok, None, *self.lp)
 
     def capture(self, pool) -> None:
         # every work item padding and every slot -1 while warming up: no KV writes, and no
-        # penalty slot on any row: the table is never touched
+        # penalty slot on any row: the table is never touched; no row asks for log-probabilities
         self.dev["slots"].fill_(-1)
         self.dev["ws"].fill_(-1)
         self.dev["pslot"].fill_(-1)
+        self.dev["nlp"].fill_(-1)
         s = torch.cuda.Stream(device=self.eng.device)
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -417,10 +456,12 @@ class _PrefillGraph:
         self.graph = g
 
     def launch(self, ids, pos, slots, cu, ws, wq, last, temp, seeds, spos, pfx=None, topk=None, topp=None,
-               pen=None):
+               pen=None, nlp=None):
         """Queue one replay for the real batch (numpy inputs, <= T tokens, <= S
-        sequences); returns (pinned token buffer, event): ``event`` completes when the
-        batch's sampled first tokens are in the buffer."""
+        sequences); returns (pinned token buffer, event, log-probabilities): ``event``
+        completes when the batch's sampled first tokens are in the buffer, and, when ``nlp``
+        (the ``logprobs`` of each sequence) is given, their (tok_lp, top_lp, top_id) in the
+        third (else None)."""
         i = self._i
         self._i ^= 1
         if self.events[i] is not None:
@@ -428,7 +469,8 @@ class _PrefillGraph:
         h = self.hosts[i]
         b = len(last)
         pslot, rep, freq, pres = pen if pen is not None else ([], [], [], [])   # (slots, r, f, p) per sequence
-        for name, arr, fill in (("pslot", pslot, -1), ("rep", rep, 1.0), ("freq", freq, 0.0), ("pres", pres, 0.0),
+        for name, arr, fill in (("nlp", nlp if nlp is not None else [], -1),
+                                ("pslot", pslot, -1), ("rep", rep, 1.0), ("freq", freq, 0.0), ("pres", pres, 0.0),
                                 ("ids", ids, 0), ("pos", pos, 0), ("slots", slots, -1), ("last", last, 0),
                                 ("seeds", seeds, 0), ("spos", spos, 0), ("temp", temp, 0.0), ("ws", ws, -1),
                                 ("wq", wq, 0), ("cu", cu, int(cu[-1])), ("pfx", pfx if pfx is not None else [], 0),
@@ -441,14 +483,21 @@ class _PrefillGraph:
         _launch_graph(self.graph, 1, self.eng.device)
         out = self.outs[i]
         out[:b].copy_(self.tok[:b], non_blocking=True)
+        lp = None
+        if nlp is not None:
+            if self.lp_outs is None:
+                self.lp_outs = [tuple(torch.zeros_like(t, device="cpu").pin_memory() for t in self.lp) for _ in range(2)]
+            lp = tuple(h[:b] for h in self.lp_outs[i])
+            for h, t in zip(lp, self.lp):
+                h.copy_(t[:b], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
         self.events[i] = ev
-        return out[:b], ev
+        return out[:b], ev, lp
 
     def run(self, *args) -> list[int]:
         """``launch`` and wait for the sampled tokens."""
-        out, ev = self.launch(*args)
+        out, ev, _ = self.launch(*args)
         ev.synchronize()
         return out.tolist()
 
@@ -474,6 +523,7 @@ class _PendingPrefill:
     event: object
     t0: float
     tokens: int
+    lp: tuple | None = None   # (tok_lp, top_lp, top_id), one column, when a request of the batch asked
 
 
 class LLMEngine:
@@ -487,7 +537,7 @@ class LLMEngine:
     def __init__(self, model: LlamaModel, kv: PagedKVCache, max_batch: int = 256, max_prefill_tokens: int = 16384,
                  max_context: int | None = None, use_graphs: bool = True, multi_step: int = 8,
                  admit_wait_s: float = 0.0, prefill_graphs: bool = True, prefix_sharing: bool = True,
-                 penalty_slots: int | None = None):
+                 penalty_slots: int | None = None, logprobs: bool = True):
         self.model, self.kv = model, kv
         # arrival batching window used by the loop that drives step() (EngineLoop):
         # an idle engine given less than a full prefill batch waits this long for more
@@ -520,6 +570,10 @@ class LLMEngine:
         if self.penalty_slots > 0 and model.tp.world == 1:
             self.penalties = PenaltyTable(self.penalty_slots, model.cfg.vocab_size,
                                           self.max_context + self.multi_step, device=self.device)
+        # log-probabilities: the kernel behind the sampler in every graph (False: none, and requests
+        # that ask are refused). A TP replica has none: its vocabulary is sharded.
+        self.logprobs = bool(logprobs) and model.tp.world == 1
+        self._lp_bufs = None   # two sets of pinned (tok_lp, top_lp, top_id), made at the first need
         self._active: _BucketState | None = None   # bucket whose device state matches self.running
         self.waiting: deque[GenRequest] = deque()
         self.running: list[GenRequest] = []
@@ -575,9 +629,10 @@ class LLMEngine:
 
     # ------------------------------------------------------------------ API
     def check_sampling(self, req: GenRequest) -> None:
-        """ValueError for top_k / top_p or a penalty out of range, or set on a tensor-parallel
-        replica (the vocabulary is sharded there and no collective computes the global threshold;
-        no penalty table is kept), or a penalty on an engine built without a penalty table."""
+        """ValueError for top_k / top_p, logprobs or a penalty out of range, or set on a
+        tensor-parallel replica (the vocabulary is sharded there and no collective computes the
+        global threshold or log-sum-exp; no penalty table is kept), or a penalty on an engine built
+        without a penalty table, or logprobs on one built without the log-probability kernel."""
         k, p = req.top_k, req.top_p
         if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= k < 2 ** 31:
             raise ValueError(f"top_k must be an integer >= 0 (0 = off), got {k!r}")
@@ -585,6 +640,14 @@ class LLMEngine:
             raise ValueError(f"top_p must be in (0, 1] (1 = off), got {p!r}")
         if (k > 0 or p < 1) and self.model.tp.world > 1:
             raise ValueError("top_k / top_p are not supported with engine.tp > 1")
+        n = req.logprobs
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not -1 <= n <= ops.LOGPROBS_MAX:
+            raise ValueError(f"logprobs must be an integer in -1..{ops.LOGPROBS_MAX} (-1 = off), got {n!r}")
+        if n >= 0:
+            if self.model.tp.world > 1:
+                raise ValueError("logprobs are not supported with engine.tp > 1")
+            if not self.logprobs:
+                raise ValueError("logprobs are not supported with engine.logprobs = false")
         # penalties: the same on a TP replica (no table over a sharded vocabulary), and refused
         # where the engine was built without a table (penalty_slots = 0)
         r, f, pp = req.repetition_penalty, req.frequency_penalty, req.presence_penalty
@@ -919,8 +982,11 @@ class LLMEngine:
             pf.event.synchronize()
         toks = pf.toks.tolist() if isinstance(pf.toks, torch.Tensor) else pf.toks
         now = time.perf_counter()
-        for r, tk in zip(pf.batch, toks):
+        lp = None if pf.lp is None else [np.asarray(t) for t in pf.lp]
+        for i, (r, tk) in enumerate(zip(pf.batch, toks)):
             r.output.append(int(tk))
+            if lp is not None and r.logprobs >= 0:
+                self._append_logprobs(r, lp, i, 0)
             r.t_first = now
             self.running.append(r)
         self._active = None  # new rows joined
@@ -957,9 +1023,11 @@ class LLMEngine:
             pen = ([r.pslot for r in batch], [r.repetition_penalty for r in batch],
                    [r.frequency_penalty for r in batch], [r.presence_penalty for r in batch])
             self._seed_penalties([r for r in batch if r.pslot >= 0])
+        nlp = [r.logprobs for r in batch] if any(r.logprobs >= 0 for r in batch) else None
+        lp = None
         g = self._prefill_graph_for(len(ids), len(batch))
         if g is not None:
-            toks, ev = g.launch(ids, pos, slots, cu, ws, wq, last, temps, seeds, full, skip, topk, topp, pen)
+            toks, ev, lp = g.launch(ids, pos, slots, cu, ws, wq, last, temps, seeds, full, skip, topk, topp, pen, nlp)
             self.stats.prefill_graph_replays += 1
             self.stats.prefill_padded_tokens += g.T - len(ids)
         else:
@@ -974,6 +1042,15 @@ class LLMEngine:
                                    t(pen[2], torch.float32), t(pen[3], torch.float32), self.penalties)
             tk = self.model.sample(logits, t(temps, torch.float32), t(seeds), t(full), top_k=t(topk, torch.int32),
                                    top_p=t(topp, torch.float32))
+            if nlp is not None:
+                b, L = len(batch), ops.LOGPROBS_MAX
+                lp = (torch.zeros(b, 1, dtype=torch.float32, device=dev), torch.zeros(b, 1, L, dtype=torch.float32, device=dev),
+                      torch.zeros(b, 1, L, dtype=torch.int32, device=dev))
+                ops.sample_logprobs(logits, t(nlp, torch.int32), None, tk, None, *lp)
+                if dev.type == "cuda":
+                    dlp, lp = lp, tuple(torch.empty(x.shape, dtype=x.dtype, pin_memory=True) for x in lp)
+                    for h, x in zip(lp, dlp):
+                        h.copy_(x, non_blocking=True)
             if dev.type == "cuda":
                 toks = torch.empty(len(batch), dtype=torch.long, pin_memory=True)
                 toks.copy_(tk, non_blocking=True)
@@ -981,7 +1058,16 @@ class LLMEngine:
                 ev.record()
             else:
                 toks, ev = tk.tolist(), None
-        return _PendingPrefill(batch, toks, ev, t0, len(ids))
+        return _PendingPrefill(batch, toks, ev, t0, len(ids), lp)
+
+    @staticmethod
+    def _append_logprobs(r: GenRequest, lp, i: int, c: int) -> None:
+        """Append row ``i``, column ``c`` of (tok_lp, top_lp, top_id) (numpy) to ``r``'s lists; list
+        entries without a token (id -1: the row had fewer non-NaN logits) are left out."""
+        tok_lp, top_lp, top_id = lp
+        r.token_logprobs.append(float(tok_lp[i, c]))
+        n = r.logprobs
+        r.top_logprobs.append([(int(a), float(b)) for a, b in zip(top_id[i, c, :n], top_lp[i, c, :n]) if a >= 0])
 
     def _seed_penalties(self, reqs: list[GenRequest]) -> None:
         """Clear the penalty slots of ``reqs`` and flag their prompts' tokens, eagerly, ahead of
@@ -1072,17 +1158,26 @@ class LLMEngine:
             else:
                 for _ in range(k):
                     g.run(False)
+        # the log-probabilities travel only for a window that holds a request that asked
+        lp = (st.tok_lp, st.top_lp, st.top_id) if self.logprobs and any(r.logprobs >= 0 for r in reqs) else None
         if self._host_bufs is not None:
             self._hb ^= 1
             host = self._host_bufs[self._hb]
             host[:B].copy_(st.hist[:B], non_blocking=True)
+            if lp is not None:
+                if self._lp_bufs is None:
+                    self._lp_bufs = [tuple(torch.empty(self.max_batch, *t.shape[1:], dtype=t.dtype, pin_memory=True)
+                                           for t in lp) for _ in range(2)]
+                dlp, lp = lp, tuple(h[:B] for h in self._lp_bufs[self._hb])
+                for h, t in zip(lp, dlp):
+                    h.copy_(t[:B], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
         else:
             host, ev = st.hist, None
         self.stats.graph_replays += k if self.use_graphs else 0
         self.stats.decode_windows += 1
-        return _Window(st, reqs, B, k, host, ev, s0)
+        return _Window(st, reqs, B, k, host, ev, s0, lp)
 
     def _consume(self, win: _Window) -> None:
         if win.event is not None:
@@ -1094,13 +1189,16 @@ class LLMEngine:
             toks = win.host[:win.B, win.s0:win.s0 + win.k].tolist()
         else:   # the window's columns wrap
             toks = win.host[:win.B].numpy()[:, [(win.s0 + i) % ms for i in range(win.k)]].tolist()
-        for r, row in zip(win.reqs, toks):
+        lp = None if win.lp is None else [np.asarray(t) for t in win.lp]
+        for i, (r, row) in enumerate(zip(win.reqs, toks)):
             if r.done:   # finished (EOS / cancel) in an earlier window: discard
                 continue
-            for tk in row:
+            for j, tk in enumerate(row):
                 if r.done_pending:
                     break
                 r.output.append(int(tk))
+                if lp is not None and r.logprobs >= 0:
+                    self._append_logprobs(r, lp, i, (win.s0 + j) % ms)
                 if (not r.ignore_eos) and int(tk) in self.eos:
                     r.done_pending = True
         self.stats.decode_tokens += win.B * win.k

@@ -16,7 +16,8 @@ for any OpenAI or Ollama client (including engine/providers.py):
   POST /api/generate | /api/chat | GET /api/tags                       (Ollama)
 
 Streaming requests get the whole completion as one chunk (SSE for OpenAI, one
-NDJSON line for Ollama). Requests are handed to the batching services
+NDJSON line for Ollama). ``logprobs`` / ``top_logprobs`` return the log-probabilities of the
+generated tokens in each format's own shape (docs/PARITY.md "Sampling: logprobs"). Requests are handed to the batching services
 (LocalMatchService / LocalExplainService), so concurrent HTTP callers share GPU
 batches with the operator's own explanations.
 """
@@ -89,6 +90,61 @@ def _penalties(src: dict, ollama: bool) -> dict:
         if n == 0:
             kw.pop("repetition_penalty", None)
     return kw
+
+
+LOGPROBS_MAX = 20   # alternatives per position at most (GenRequest.logprobs)
+
+
+def _logprobs(body: dict, chat: bool, ollama: bool) -> int:
+    """``GenRequest.logprobs`` of a request body (-1 = off). OpenAI chat and both Ollama endpoints:
+    ``logprobs`` is a boolean and ``top_logprobs`` an integer in 0..20 that needs ``logprobs``
+    true; OpenAI completions: ``logprobs`` is that integer itself. Absent or null means off;
+    booleans are no integers."""
+    def count(name: str) -> int:
+        v = body[name]
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or v != int(v) or not 0 <= v <= LOGPROBS_MAX:
+            raise BadRequest(f"'{name}' must be an integer in 0..{LOGPROBS_MAX}, got {v!r}")
+        return int(v)
+
+    on = body.get("logprobs")
+    if not chat and not ollama:
+        return -1 if on is None else count("logprobs")
+    if on is not None and not isinstance(on, bool):
+        raise BadRequest(f"'logprobs' must be a boolean, got {on!r}")
+    if body.get("top_logprobs") is None:
+        return 0 if on else -1
+    n = count("top_logprobs")
+    if not on:
+        raise BadRequest("'top_logprobs' needs 'logprobs': true")
+    return n
+
+
+def _json_lp(v: float):
+    """JSON has no infinities: -inf travels as -9999.0 (the vLLM convention), NaN as null."""
+    if v != v:
+        return None
+    return math.copysign(9999.0, v) if math.isinf(v) else v
+
+
+def _chat_logprobs(entries: list[dict]) -> list[dict]:
+    """The OpenAI chat ``logprobs.content`` list (also Ollama's ``logprobs``) of ExplainEngine's entries."""
+    one = lambda e: {"token": e["token"], "logprob": _json_lp(e["logprob"]), "bytes": e["bytes"]}  # noqa: E731
+    return [{**one(e), "top_logprobs": [one(t) for t in e["top"]]} for e in entries]
+
+
+def _completion_logprobs(entries: list[dict]) -> dict:
+    """The OpenAI completions ``logprobs`` object: parallel lists, alternatives as {token text:
+    logprob} (of two ids with one text the more likely stays), offsets into the completion text."""
+    tops, offs, off = [], [], 0
+    for e in entries:
+        d = {}
+        for t in e["top"]:
+            d.setdefault(t["token"], _json_lp(t["logprob"]))
+        tops.append(d)
+        offs.append(off)
+        off += len(e["token"])
+    return {"tokens": [e["token"] for e in entries], "token_logprobs": [_json_lp(e["logprob"]) for e in entries],
+            "top_logprobs": tops, "text_offset": offs}
 
 
 def _sampling(body: dict, ollama: bool) -> dict:
@@ -175,6 +231,9 @@ class CompatServer:
                 ollama = p.startswith("/api/")
                 chat = p in ("/chat/completions", "/api/chat")
                 kw = _sampling(body, ollama)
+                nlp = _logprobs(body, chat, ollama)
+                if nlp >= 0:   # only when asked: every other request reaches the engine as before
+                    kw["logprobs"] = nlp
                 if chat:
                     out = srv.explainer.complete(messages=_messages(body), model=body.get("model"), **kw)
                 else:
@@ -196,6 +255,8 @@ class CompatServer:
                         obj["message"] = {"role": "assistant", "content": out["text"]}
                     else:
                         obj["response"] = out["text"]
+                    if nlp >= 0:
+                        obj["logprobs"] = _chat_logprobs(out["logprobs"])
                     if body.get("stream", True):   # Ollama streams by default: one final NDJSON line
                         self._send(200, json.dumps(obj).encode() + b"\n", "application/x-ndjson")
                     else:
@@ -203,18 +264,21 @@ class CompatServer:
                     return True
                 usage = {"prompt_tokens": out["prompt_tokens"], "completion_tokens": out["completion_tokens"],
                          "total_tokens": out["prompt_tokens"] + out["completion_tokens"]}
+                lp = None
+                if nlp >= 0:
+                    lp = {"content": _chat_logprobs(out["logprobs"])} if chat else _completion_logprobs(out["logprobs"])
                 base = {"id": ("chatcmpl-" if chat else "cmpl-") + uuid.uuid4().hex[:24], "created": int(time.time()),
                         "model": model}
                 if body.get("stream"):   # SSE: the whole completion as one chunk, then [DONE]
                     delta = ({"delta": {"role": "assistant", "content": out["text"]}} if chat else {"text": out["text"]})
                     chunk = {**base, "object": "chat.completion.chunk" if chat else "text_completion",
-                             "choices": [{"index": 0, **delta, "finish_reason": out["finish_reason"]}]}
+                             "choices": [{"index": 0, **delta, "logprobs": lp, "finish_reason": out["finish_reason"]}]}
                     self._send(200, b"data: " + json.dumps(chunk).encode() + b"\n\ndata: [DONE]\n\n",
                                "text/event-stream")
                     return True
                 choice = ({"message": {"role": "assistant", "content": out["text"]}} if chat else {"text": out["text"]})
                 self._send(200, {**base, "object": "chat.completion" if chat else "text_completion",
-                                 "choices": [{"index": 0, **choice, "finish_reason": out["finish_reason"]}],
+                                 "choices": [{"index": 0, **choice, "logprobs": lp, "finish_reason": out["finish_reason"]}],
                                  "usage": usage})
                 return True
 
@@ -241,7 +305,7 @@ class CompatServer:
                 except Exception as e:  # noqa: BLE001
                     msg = str(e)
                     if "exceeds max_context" in msg or "top_k / top_p are not supported" in msg \
-                            or "penalties are not supported" in msg:
+                            or "penalties are not supported" in msg or "logprobs are not supported" in msg:
                         return self._send(400, {"error": {"message": msg, "type": "invalid_request_error"}})
                     log.error("request %s failed: %s", self.path, e)
                     return self._send(504 if "timed out" in msg else 500, {"error": {"message": msg}})

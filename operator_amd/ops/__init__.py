@@ -19,7 +19,7 @@ from .gemm import (BLAS_CALLS, BLAS_PLANNED, GEMM_DECODE_M, GU_BLOCK, LM_HEAD_MI
 
 __all__ = [
     "rmsnorm", "silu_mul", "embedding", "rope_kv", "attn_prefill", "attn_decode", "attn_decode_rope", "sample",
-    "sample_threshold", "penalty_seed", "sample_penalty",
+    "sample_threshold", "penalty_seed", "sample_penalty", "sample_logprobs", "LOGPROBS_MAX",
     "kernels", "patterns", "native_available", "reference", "prefill_work_list", "prefill_block_q", "prefill_variant", "decode_splits",
     "decode_workspace", "linear", "gemm_plan", "gemm_table", "gate_up_silu", "interleave_gate_up",
     "quantize_fp8", "silu_quantize_fp8", "linear_fp8", "fp8_plan", "SplitK", "linear_tile", "tile_ok", "BLAS_CALLS",
@@ -429,6 +429,25 @@ def sample_penalty(logits: torch.Tensor, pslot: torch.Tensor, last_tok: torch.Te
         return logits
     kernels().sample_penalty(logits, pslot, last_tok, ctx, rep, freq, pres, table.cnt, table.lst, table.n)
     return logits
+
+
+LOGPROBS_MAX = reference.LOGPROBS_MAX   # most likely tokens reported per position (kernels.h kLogprobsMax)
+
+
+def sample_logprobs(logits: torch.Tensor, nlp: torch.Tensor, ctx: torch.Tensor | None, tokens: torch.Tensor,
+                    step: torch.Tensor | None, tok_lp: torch.Tensor, top_lp: torch.Tensor,
+                    top_id: torch.Tensor) -> None:
+    """Log-probabilities (log-softmax at temperature 1 of ``logits`` [rows, vocab] as they are:
+    after the penalties, before temperature and top-k / top-p) of the sampled ``tokens`` (int64
+    per row) and of each row's ``nlp[i]`` (int32; 0..LOGPROBS_MAX) most likely tokens; semantics:
+    ``reference.sample_logprobs``. A row with ``nlp[i]`` < 0, or with ``ctx[i]`` (int32 per row) ==
+    0, is not read. Written at column ``step[0] % C`` (``step`` int64 [1]; None: column 0) of
+    ``tok_lp`` fp32 [rows, C], ``top_lp`` fp32 and ``top_id`` int32 [rows, C, LOGPROBS_MAX]: the
+    token's value and the first ``nlp[i]`` list entries, nothing else. It only reads ``logits``."""
+    if not logits.is_cuda:
+        reference.sample_logprobs(logits, nlp, ctx, tokens, step, tok_lp, top_lp, top_id)
+        return
+    kernels().sample_logprobs(logits, nlp, ctx, tokens, step, tok_lp, top_lp, top_id)
 
 
 def sample(logits: torch.Tensor, temperature: torch.Tensor, seeds: torch.Tensor, positions: torch.Tensor,

@@ -363,6 +363,52 @@ def sample_penalty(logits: torch.Tensor, pslot: torch.Tensor, last_tok: torch.Te
         logits[row, idx] = torch.where(torch.isnan(x), x, y.to(logits.dtype))
 
 
+LOGPROBS_MAX = 20   # list entries per position (kernels.h kLogprobsMax)
+
+
+def sample_logprobs(logits: torch.Tensor, nlp: torch.Tensor, ctx: torch.Tensor | None, tokens: torch.Tensor,
+                    step: torch.Tensor | None, tok_lp: torch.Tensor, top_lp: torch.Tensor, top_id: torch.Tensor) -> None:
+    """Log-probabilities of the sampled ``tokens`` and of each row's most likely tokens, fp64 and
+    sort-based (docs/PARITY.md "Sampling: logprobs"). Row r with ``nlp[r]`` >= 0 (and ``ctx[r]``
+    != 0 when ``ctx`` is given) writes column c = ``step[0] % C`` (0 without ``step``) of ``tok_lp``
+    [rows, C] fp32 and the first N = min(nlp[r], LOGPROBS_MAX) entries of ``top_lp`` fp32 /
+    ``top_id`` int32 [rows, C, LOGPROBS_MAX]; every other element keeps its value.
+
+    * lse = mx + ln(sum over non-NaN x of exp(x - mx)), mx the maximum over non-NaN logits, a term
+      with x == mx counting as exactly 1 (also for mx = +-inf); logprob(t) = x_t - lse, so NaN for a
+      NaN logit, for every token of a row without a non-NaN logit or with mx = -inf, and for a
+      token id outside the row;
+    * the list: the first min(N, number of non-NaN logits) tokens by (logit descending, id
+      ascending), -0 and +0 one value; the remaining entries are id -1, log-probability -inf."""
+    V, C = logits.shape[1], tok_lp.shape[1]
+    col = int(step.reshape(-1)[0]) % C if step is not None else 0
+    for r in range(logits.shape[0]):
+        n = int(nlp[r])
+        if n < 0 or (ctx is not None and int(ctx[r]) == 0):
+            continue
+        n = min(n, LOGPROBS_MAX)
+        x = logits[r].double().cpu()
+        ok = ~torch.isnan(x)
+        xv = x[ok]
+        lse = torch.tensor(math.nan, dtype=torch.float64)
+        if xv.numel():
+            mx = xv.max()
+            w = torch.exp(xv - mx)
+            w[xv == mx] = 1.0                 # also for mx = +-inf (inf - inf)
+            lse = mx + torch.log(w.sum())
+        t = int(tokens[r])
+        tok_lp[r, col] = float(x[t] - lse) if 0 <= t < V else math.nan
+        if n == 0:
+            continue
+        ids = torch.nonzero(ok).flatten()
+        order = torch.sort(-xv, stable=True).indices[:n]   # ids ascend already; -0 == +0 under the sort
+        m = order.numel()
+        top_id[r, col, :m] = ids[order].to(top_id.dtype)
+        top_lp[r, col, :m] = (xv[order] - lse).to(top_lp.dtype)
+        top_id[r, col, m:n] = -1
+        top_lp[r, col, m:n] = -math.inf
+
+
 def sample(logits: torch.Tensor, temperature: torch.Tensor, seeds: torch.Tensor,
            positions: torch.Tensor) -> torch.Tensor:
     return sample_shard(logits, temperature, seeds, positions)[0]

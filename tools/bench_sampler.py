@@ -14,6 +14,11 @@ feature. One JSON line per arm on stdout (and appended to --out).
 --penalties measures the repetition / frequency / presence penalty kernel the same way, three
 arms: the defaults step; the same behind sample_penalty with no row holding a slot (what every
 decode step launches now); the same with every row penalised over --seen distinct tokens.
+
+--logprobs measures the log-probability kernel behind the sampler the same way, four arms: the
+defaults step; the same followed by sample_logprobs with every row off (what every decode step
+launches now); with every row asking for its token's value only (N = 0); with every row asking
+for 20 alternatives.
 """
 import argparse
 import json
@@ -37,6 +42,9 @@ ap.add_argument("--out", default=None)
 ap.add_argument("--penalties", action="store_true",
                 help="the penalty arms in place of the filter arms: the defaults step, the same behind the "
                      "penalty kernel with every row off, and with every row on")
+ap.add_argument("--logprobs", action="store_true",
+                help="the log-probability arms in place of the filter arms: the defaults step, the same followed by "
+                     "the logprob kernel with every row off, every row at N = 0, every row at N = 20")
 ap.add_argument("--seen", type=int, default=1100, help="distinct seen tokens per row of the rows-on arm")
 a = ap.parse_args()
 
@@ -75,7 +83,26 @@ def penalty_arm(on: bool):
     return lambda: ops.sample_penalty(x, pslot, last, ctx, rep, freq, pres, tb)
 
 
-if a.penalties:
+def logprob_arm(n: int):
+    """sample_logprobs behind the defaults step as a decode graph runs it (the device step counter,
+    eight columns, every row live by its context length), every row asking for ``n``."""
+    C, L = 8, ops.LOGPROBS_MAX
+    nlp = torch.full((B,), n, dtype=torch.int32, device="cuda")
+    ctx = torch.full((B,), 1100, dtype=torch.int32, device="cuda")
+    step = torch.full((1,), 3, dtype=torch.long, device="cuda")
+    tok_lp = torch.zeros(B, C, dtype=torch.float32, device="cuda")
+    top_lp = torch.zeros(B, C, L, dtype=torch.float32, device="cuda")
+    top_id = torch.zeros(B, C, L, dtype=torch.int32, device="cuda")
+    return lambda: ops.sample_logprobs(x, nlp, ctx, out, step, tok_lp, top_lp, top_id)
+
+
+post = {}   # arm -> what runs behind the sampler
+if a.logprobs:
+    bench = "sampler_logprobs"
+    arms = {n: (None, filt(0, 1.0)) for n in ("defaults", "logprob_kernel_rows_off", "logprob_rows_n0", "logprob_rows_n20")}
+    post = {"logprob_kernel_rows_off": logprob_arm(-1), "logprob_rows_n0": logprob_arm(0),
+            "logprob_rows_n20": logprob_arm(20)}
+elif a.penalties:
     bench = "sampler_penalty"
     arms = {"defaults": (None, filt(0, 1.0)), "penalty_kernel_rows_off": (penalty_arm(False), filt(0, 1.0)),
             f"penalty_rows_on_{a.seen}_seen": (penalty_arm(True), filt(0, 1.0))}
@@ -85,15 +112,17 @@ else:
             "top_k+top_p": (None, filt(40, 0.9))}
 
 
-def call(pre, kw):
+def call(pre, kw, after=None):
     if pre is not None:
         pre()
     ops.sample(x, t, sd, ps, out=out, **kw)
+    if after is not None:
+        after()
 
 
-for pre, kw in arms.values():
+for n, (pre, kw) in arms.items():
     for _ in range(3):
-        call(pre, kw)
+        call(pre, kw, post.get(n))
 torch.cuda.synchronize()
 us = {n: [] for n in arms}
 for _ in range(a.rounds):
@@ -101,7 +130,7 @@ for _ in range(a.rounds):
         e0, e1 = torch.cuda.Event(True), torch.cuda.Event(True)
         e0.record()
         for _ in range(a.calls):
-            call(pre, kw)
+            call(pre, kw, post.get(n))
         e1.record()
         torch.cuda.synchronize()
         us[n].append(e0.elapsed_time(e1) / a.calls * 1e3)
